@@ -10,6 +10,11 @@ frames per sequence), event-frames/s aggregated over all ranks.
 A "step" = one full training step with inputs already resident in HBM: LSTM-row reset, 21 backbone
 timesteps, PAFPN + head + SimOTA + losses on the 32 labelled frames, backward, gradient all-reduce (RCCL),
 value-clip + AdamW, OneCycle LR.  Nothing is skipped or cached.  Rank 0 prints ONE JSON line.
+Every step starts from the same weights and optimiser state (the initial ones), so that what a step computes is the same every run.
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds the measurements that take runs of their
+own: the roofline / per-family kernel probe, the host enqueue time, the other precision mode and the CPU baseline (each can still
+be turned off with its --no-* option).  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -33,8 +38,22 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 MFMA peak (MI355X_MICROARCH.md; AMD
 # 29.01 MB of PAFPN + head per labelled frame) + 395/168 MB of optimiser traffic = 76.5 MB; with fp32 activations twice the activation part
 CFG_PRECISION = {'16f': 16, 'bf16': 'bf16', 'f32': 32}      # training.precision per bench mode (16 = the reference's fp16 autocast -> mode 16f)
 DTYPE_NAME = {'16f': 'fp16', 'bf16': 'bf16', 'f32': 'f32'}   # the JSON line's dtype: the operand type of the forward contractions
+DUMP_MAX_ELEMS = 12 * 2 ** 20   # float32 state elements --dump-outputs writes at most (48 MiB; RVT-S has 9.9 M)
 ALGO_MB_PER_FRAME = {'bf16': 68.61 + 32.0 / 168.0 * 29.01 + 395.0 / 168.0,
                      'f32': 2 * (68.61 + 32.0 / 168.0 * 29.01) + 395.0 / 168.0}
+
+
+def step_outputs(module, out):
+    """What a caller of ``fit_step`` holds after a step, as host arrays: the loss terms it returned (float64, one file each) and the
+    module's floating-point state after the optimiser step (parameters, BatchNorm statistics) in state_dict order, flattened to
+    one float32 vector; above DUMP_MAX_ELEMS elements a fixed seeded sample of it (the same indices on every run)."""
+    arrays = {k.replace('/', '_'): np.array([float(v.detach())], np.float64) for k, v in out['log_dict'].items()}
+    state = torch.cat([v.detach().reshape(-1).float() for v in module.state_dict().values() if v.is_floating_point()])
+    if state.numel() > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(state.numel(), DUMP_MAX_ELEMS, replace=False))
+        state = state[torch.from_numpy(idx).to(state.device)]
+    arrays['state'] = state.cpu().numpy()
+    return arrays
 
 
 def _native_comm_active():
@@ -298,7 +317,17 @@ def main():
     ap.add_argument('--dump-calls', default='', help='file for the per-launch table (C entry point, shape arguments, us) of the probe steps')
     ap.add_argument('--pseudo', action='store_true', help='the pseudo-label inference pass of BASELINE configs[4] (single-GPU leg) instead of '
                     'the training step: PseudoLabeler.predict_step, --batch source streams + hflip TTA, --seq-len frames per chunk')
+    ap.add_argument('--full', action='store_true', help='also run the measurements that take runs of their own: roofline / kernel-family '
+                    'probe, host enqueue time, the other precision mode, the CPU baseline (default: the timed steps alone)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step computed (loss terms, module state '
+                    'after the optimiser step) as DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full:
+        args.no_roofline = args.no_second_dtype = args.no_cpu_baseline = True
+        if args.dump_calls:
+            ap.error('--dump-calls records the probe steps of --full')
+    if args.pseudo and args.dump_outputs:
+        ap.error('--dump-outputs covers the training step, not --pseudo')
     if args.pseudo:
         if not torch.cuda.is_available():
             raise SystemExit('bench.py needs an MI355X (no CPU fallback for the HIP path)')
@@ -328,9 +357,9 @@ def main():
     T, B = args.seq_len, args.batch
     label_ts = tuple(t for t in (4, 9, 14, 19) if t < T) or (T - 1,)
 
-    def measure(dtype, steps, warmup, want_roofline):
+    def measure(dtype, steps, warmup, want_roofline, want_dump=False):
         """One full measurement in precision mode ``dtype``: fresh module (same seed), warm-up, K timed steps between barriers,
-        optional roofline probe.  -> dict(dt, loss, roofline, module)."""
+        optional roofline probe, optional copy of the last timed step's outputs.  -> dict(dt, loss, roofline, module, dump)."""
         # The product path, through the reference's own surface (train.py:131-133,228-250): fetch_model_module(config) ->
         # Module.setup('fit') -> configure_optimizers() -> per batch what Lightning's automatic optimisation does
         # (optimizer.step(closure: zero_grad, training_step, backward), scheduler.step()).
@@ -386,8 +415,21 @@ def main():
             torch.cuda.synchronize()
 
         step_no = [0]
+        # Every step trains from the same state: the initial weights and an empty AdamW.  The weight gradients accumulate with fp32
+        # atomics whose order varies from run to run; one step from a fixed state reproduces to rounding, a trajectory of steps
+        # amplifies those last bits into per-cent differences.  The restore is three flat-buffer copies on the launch stream.
+        flat = opt.flat
+        start = (flat.data.clone(), flat.exp_avg.clone(), flat.exp_avg_sq.clone(), flat.step_count)
+
+        def restart():
+            flat.data.copy_(start[0])
+            flat.exp_avg.copy_(start[1])
+            flat.exp_avg_sq.copy_(start[2])
+            flat.step_count = start[3]
+            flat.touch()                                      # derived weight copies (packs, bf16 shadow) are stale
 
         def run(mask):
+            restart()
             out = fit_step(module, opt, sched, loader_batch(mask), step_no[0])
             step_no[0] += 1
             return out
@@ -411,19 +453,21 @@ def main():
         if dist.is_initialized():
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
         dt = float(t_max)
+        dump = step_outputs(module, out) if want_dump else None      # before any further step changes the module
         # host side of one step: enqueue time of single steps launched into an IDLE device (inside the timed loop the host runs ahead of
         # the GPU and its launch calls block on the full hardware queue, so the loop's own host time says nothing)
         host_ms = []
-        for s in range(5):
+        for s in range(5 if args.full else 0):
             m = first_mask(2 + s)
             b = loader_batch(m)
+            restart()
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             fit_step(module, opt, sched, b, step_no[0])
             host_ms.append(1e3 * (time.perf_counter() - t1))
             step_no[0] += 1
         torch.cuda.synchronize()
-        host_ms = sorted(host_ms)[len(host_ms) // 2]
+        host_ms = sorted(host_ms)[len(host_ms) // 2] if host_ms else None
         plan_info = module._plans.info() if module.plan_mode else None
         if plan_info is not None:
             # the plan cache over the TIMED steps alone (warm-up and the probe steps excluded)
@@ -480,10 +524,10 @@ def main():
         launch = (f'{how}, schedule={"batched" if module.time_batched else "timestep"}, wgrad side stream {"on" if module.wgrad_side else "off"}, '
                   f'precision mode {ops.get_precision()}')
         return dict(dt=dt, loss=loss_val, roofline=roofline, roofline_gemm=roofline_gemm, family_ms=family_ms, launch=launch, family_ms_all=family_all,
-                    host_ms=host_ms, plan_info=plan_info, probe_note=probe_note,
+                    host_ms=host_ms, plan_info=plan_info, probe_note=probe_note, dump=dump,
                     calls=(len(probe.calls) // probe.steps if probe is not None else None))
 
-    main_run = measure(args.dtype, args.steps, args.warmup, not args.no_roofline)
+    main_run = measure(args.dtype, args.steps, args.warmup, not args.no_roofline, want_dump=bool(args.dump_outputs) and rank == 0)
     dt, loss_val, roofline, launch = main_run['dt'], main_run['loss'], main_run['roofline'], main_run['launch']
     other = None
     if world == 1 and headline and not args.no_second_dtype:
@@ -525,11 +569,11 @@ def main():
                        'family_ms_per_step': main_run['family_ms'],
                        # host side: wall time of the Python call chain of ONE step launched into an idle device (median of 5), the kernels
                        # of the step's launch plans (+ ~12 eager launches: zero-grad, copy-ins, optimiser) or, eager, the C calls of a step
-                       'host_enqueue_ms_per_step': round(main_run['host_ms'], 3),
+                       'host_enqueue_ms_per_step': round(main_run['host_ms'], 3) if main_run['host_ms'] is not None else None,
                        'kernel_ms_per_step': round(sum((main_run['family_ms_all'] or {}).values()), 3) if main_run.get('family_ms_all') else None,
                        'launches_per_step': (main_run['plan_info']['forward']['kernels'] + main_run['plan_info']['backward']['kernels'] + 12)
                        if main_run['plan_info'] else None,
-                       'c_calls_per_eager_step': main_run['calls'], 'probe_steps': PROBE_STEPS, 'probe_note': main_run['probe_note'],
+                       'c_calls_per_eager_step': main_run['calls'], 'probe_steps': PROBE_STEPS if not args.no_roofline else None, 'probe_note': main_run['probe_note'],
                        'launch_plans': main_run['plan_info']},
             'roofline': roofline,
             'roofline_linear_gemm': main_run['roofline_gemm'],
@@ -538,6 +582,10 @@ def main():
             out['other_precision'] = other          # the same workload and step in the other precision mode, measured in this run
         if not args.no_cpu_baseline and world == 1 and headline:
             out['cpu_baseline'] = cpu_baseline_bounded()
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in main_run['dump'].items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.barrier()
