@@ -65,8 +65,8 @@ int leod_partition_attn_bwd(const float* qkv, const float* dout, const float* ls
 int leod_partition_attn_16bit_ok(int B, int H, int W, int C, int heads, int ph, int pw);
 /* Bit 1 of qkv_bf16 in the two attention calls above: the attention output `out` (forward) is written / its gradient `dout` (backward)
  * is read as bf16 rows [M,C] -- valid where leod_partition_attn_o16_ok returns 1 (bf16-tile kernels).  leod_attn_block_o16_ok adds the
- * conditions of the block's other consumers (leod_linear_lsres_bf16_fwd, bit 1 of dy_bf16 in leod_linear_dgrad = dx written as bf16 rows,
- * bit 1 of dy_bf16 in leod_linear_wgrad = x holds bf16 rows): the reference's autocast holds both tensors in 16 bits as well
+ * conditions of the block's other consumers (leod_linear_lsres_bf16_fwd, dx_fmt 1 of leod_linear_dgrad = dx written as bf16 rows,
+ * x_fmt 3 of leod_linear_wgrad = x holds bf16 rows): the reference's autocast holds both tensors in 16 bits as well
  * (maxvit.py:185-270 under train.py:236-243). */
 int leod_partition_attn_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw);
 int leod_attn_block_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw);
@@ -86,8 +86,7 @@ int leod_linear_lsres_gelu16_fwd(const void* u16, const float* W, const float* b
                                  int M, int N, int K, leod_stream_t stream);
 int leod_linear_dgrad_gelu16(const float* dy, const float* kscale, const float* W, const void* u16, void* dx, int M, int N, int K,
                              int out_bf16, leod_stream_t stream);
-int leod_linear_wgrad_gelu16(const float* dy, long lddy, const void* u16, float* dW, float* dbias, int M, int N, int K,
-                             leod_stream_t stream);
+/* (the fc2 weight gradient on u16 is x_fmt 2 of leod_linear_wgrad / leod_linear_wgrad_group) */
 
 /* n <= 4 Linear weight gradients of ONE row count M in one preparation, one contraction and one reduce launch (LDS-DMA kernel with a problem
  * table): dW_k [N_k, K_k] += dy_k^T X_k, dbias_k += colsum(dy_k).  The four weight gradients of an attention block, which its backward issues
@@ -150,14 +149,16 @@ int leod_convlstm_seq_bwd(const float* dh_seq, const float* dc_last, const float
  * bf16 rows [T][M][4C] -- the reference's autocast holds the gates in 16 bits as well (rnn.py:58-62 under train.py:236-243). */
 int leod_convlstm_seq_gates16_ok(int C);
 
-/* dy_bf16 (here and in leod_linear_wgrad / leod_linear_dgrad_lnbwd): dy points to bf16 elements -- in precision mode bf16 the wide
- * gradients du (out_bf16 of leod_linear_dgrad_gelu16) and dqkv are stored as the bf16 their consumers feed to the MFMAs anyway.
+/* dy_fmt 1 (here and in leod_linear_wgrad; dy_bf16 of leod_linear_dgrad_lnbwd): dy points to bf16 elements -- in precision mode bf16 the
+ * wide gradients du (out_bf16 of leod_linear_dgrad_gelu16) and dqkv are stored as the bf16 their consumers feed to the MFMAs anyway.
+ * dy_fmt 0: fp32 rows.  dx_fmt: 0 fp32, 1 dx is written as bf16 rows (precision mode bf16, plain dgrad without dx2 / colsum / accumulate /
+ * dres / aux_u / nsplit on the LDS-staged kernels; -3 otherwise).
  * dx (=|+=) (dy[M,N]*kscale[N]) W[N,K] ; optional: multiply by gelu'(aux_u[M,K]); route columns >= nsplit to dx2;
  * colsum[K] += column sums of the result; dres [M,K] (optional, leading dimension lddx): dx = dres + result (the second gradient source of a
  * residual branch, so that no separate add kernel runs).  Autograd of the Linear layers above. */
 int leod_linear_dgrad(const float* dy, long lddy, const float* kscale, const float* W, float* dx, long lddx, float* dx2,
                       long lddx2, int nsplit, const float* aux_u, float* colsum, int accumulate, const float* dres, int M, int N,
-                      int K, int dy_bf16, leod_stream_t stream);
+                      int K, int dy_fmt, int dx_fmt, leod_stream_t stream);
 /* Workspace of the weight-gradient calls below for launches on `stream` (precision mode bf16: the per-workgroup partial tiles that a second
  * kernel adds up -- 1024 workgroups adding to the same dW addresses with atomics were 130 us of a 200 us launch): leod_workspace_bytes()
  * bytes, 16-byte aligned, owned by the caller and kept alive until replaced (ws == NULL withdraws it).  Without a registered workspace
@@ -165,10 +166,13 @@ int leod_linear_dgrad(const float* dy, long lddy, const float* kscale, const flo
  * (No counterpart in the reference: torch's autograd owns the cuBLAS workspaces there.) */
 long leod_workspace_bytes(void);
 int leod_set_workspace(void* ws, long bytes, leod_stream_t stream);
-/* dW[N,K] += dy^T X ; dbias[N] += colsum(dy) ; X = x, LN(x) (stats, ln_w, ln_b) or [x | x2] (K1 = cols of x). */
+/* dW[N,K] += dy^T X ; dbias[N] += colsum(dy).  dy_fmt: 0 fp32 rows, 1 bf16 rows.  x_fmt, as in leod_linear_wgrad_group: what x points to
+ * and how X comes from it -- 0 fp32 rows, 1 fp32 rows through LayerNorm (stats [M,2], ln_w, ln_b: all three, and stats only here),
+ * 2 fp16 pre-activation through GELU (fp32 dy, no x2), 3 bf16 rows, 4 fp16 rows (3 / 4: no x2; -3 where no bf16-MFMA kernel covers the
+ * shape).  x2 != NULL: X = [x | x2] with K1 columns from x and fp32 x2.  -1 for any other combination. */
 int leod_linear_wgrad(const float* dy, long lddy, const float* x, long ldx, const float* stats, const float* ln_w,
                       const float* ln_b, const float* x2, long ldx2, int K1, float* dW, float* dbias, int M, int N,
-                      int K, int dy_bf16, leod_stream_t stream);
+                      int K, int dy_fmt, int x_fmt, leod_stream_t stream);
 
 /* LayerNorm over channels (eps 1e-5), maxvit.py:172-178 and its autograd. */
 int leod_layernorm_fwd(const float* x, const float* w, const float* b, float* y, float* stats, int M, int C, float eps,

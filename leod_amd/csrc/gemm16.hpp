@@ -26,6 +26,27 @@
 #include <stdlib.h>
 #include "common.hpp"
 
+// Storage format of a row operand (ALRows::fmt, XRows::fmt) or of a row store (EpStore::out_fmt / aux_fmt).  The values are template
+// arguments of the loaders (ALRowsM<F, ..>), so they are part of the kernel names: keep them.
+enum RowFmt : int {
+    FMT_F32 = 0,        // fp32 rows
+    FMT_F16PRE = 1,     // fp16 PRE-activation of the MLP hidden: a loader returns gelu(x); as a store format plain fp16, clamped to its range
+    FMT_BF16 = 2,       // bf16 rows
+    FMT_F16 = 3         // fp16 rows, read as they are (precision mode 16f: the attention output)
+};
+// What the X operand of a Linear weight gradient is: the x_fmt of the C ABI (leod_linear_wgrad, leod_linear_wgrad_group), XRows::x_mode(),
+// the XM template argument of the weight-gradient kernels.  A concat source (XRows::x2) is orthogonal to it.
+enum XMode : int {
+    XM_ROWS = 0,        // fp32 rows
+    XM_LN = 1,          // fp32 rows through LayerNorm with saved (mean, rstd)
+    XM_GELU16 = 2,      // fp16 pre-activation through GELU
+    XM_BF16 = 3,        // bf16 rows
+    XM_F16 = 4          // fp16 rows
+};
+static inline bool xm_valid(int xm) { return xm >= XM_ROWS && xm <= XM_F16; }
+static inline bool xm_is16(int xm) { return xm >= XM_GELU16; }          // x holds 16-bit elements
+static inline bool xm_is_mfma_operand(int xm) { return xm == XM_BF16; }  // the bf16 MFMA operand as stored: needs no preparation pass
+
 // =================================================================================================
 // A loaders (row operand).  init() is called by all 64 lanes (may shuffle); load() returns the float4
 // A(row, k..k+3) or zeros when out of range.
@@ -37,7 +58,7 @@ struct ALRows {                 // plain rows, optional LayerNorm prologue, opti
     float* stats_out;                                   // optional [M,2] (mean, rstd) written by n-block 0
     int K;                                              // row length used for the LN statistics
     const float* stats_in;                              // optional precomputed [M,2] (mean, rstd): skips the statistics passes
-    int fmt;                                            // 2: bf16 rows; 3: fp16 rows (plain); 0: x is fp32; 1: x is an fp16 PRE-activation, A = gelu(x) (the MLP hidden of stages 1-2 is stored
+    int fmt;                                            // RowFmt.  FMT_F16PRE: A = gelu(x) (the MLP hidden of stages 1-2 is stored
                                                         // once, as fp16, in precision mode bf16: maxvit.py:110-118 under the reference's autocast)
     struct St { const float* p; float mean, rstd; bool ok; };
     __device__ __forceinline__ int klen(const St&, int K) const { return K; }
@@ -66,18 +87,18 @@ struct ALRows {                 // plain rows, optional LayerNorm prologue, opti
     }
     __device__ __forceinline__ f4 load(const St& s, int k, int Kt) const {
         if (k >= Kt) return zero4();
-        if (fmt == 1) {
+        if (fmt == FMT_F16PRE) {
             f4 v = unpack_h16(*reinterpret_cast<const s4*>(reinterpret_cast<const unsigned short*>(s.p) + k));
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = gelu_erf(v[j]);
             return s.ok ? v : zero4();
         }
-        if (fmt == 2) {                                  // bf16 gradient rows (precision mode bf16: du / dqkv are stored as the bf16 the MFMAs consume)
+        if (fmt == FMT_BF16) {                           // bf16 gradient rows (precision mode bf16: du / dqkv are stored as the bf16 the MFMAs consume)
             f4 v = unpack_bf16(*reinterpret_cast<const s4*>(reinterpret_cast<const unsigned short*>(s.p) + k));
             if (kscale) v = v * ld4(kscale + k);
             return s.ok ? v : zero4();
         }
-        if (fmt == 3) {                                  // fp16 activation rows (precision mode 16f: the attention output)
+        if (fmt == FMT_F16) {                            // fp16 activation rows (precision mode 16f: the attention output)
             f4 v = unpack_h16(*reinterpret_cast<const s4*>(reinterpret_cast<const unsigned short*>(s.p) + k));
             return s.ok ? v : zero4();
         }
@@ -101,7 +122,7 @@ struct ALRowsM : ALRows {
     static constexpr bool kTwoPhase = true;
     struct Raw { f4 v; u2_ h; f4 g, b, s; };
     __device__ __forceinline__ void raw(const St& st, int k, Raw& r) const {
-        if constexpr (FMT == 0) r.v = ld4(st.p + k);
+        if constexpr (FMT == FMT_F32) r.v = ld4(st.p + k);
         else r.h = *reinterpret_cast<const u2_*>(reinterpret_cast<const unsigned short*>(st.p) + k);
         if constexpr (LN) { r.g = ld4(ln_w + k); r.b = ld4(ln_b + k); }
         if constexpr (KS) r.s = ld4(kscale + k);
@@ -109,7 +130,7 @@ struct ALRowsM : ALRows {
     // split form for kernels whose staging slots of a thread share ONE k offset (gemm_wide_bf16_kernel): the row data per slot, the
     // per-k vectors (LayerNorm weight / bias, scale) once per chunk into the Raw of slot 0
     __device__ __forceinline__ void raw_x(const St& st, int k, Raw& r) const {
-        if constexpr (FMT == 0) r.v = ld4(st.p + k);
+        if constexpr (FMT == FMT_F32) r.v = ld4(st.p + k);
         else r.h = *reinterpret_cast<const u2_*>(reinterpret_cast<const unsigned short*>(st.p) + k);
     }
     __device__ __forceinline__ void raw_k(int k, Raw& r) const {
@@ -118,12 +139,12 @@ struct ALRowsM : ALRows {
     }
     __device__ __forceinline__ f4 fin_k(const St& st, const Raw& r, const Raw& rk) const {
         f4 v;
-        if constexpr (FMT == 1) {
+        if constexpr (FMT == FMT_F16PRE) {
             v = unpack_h16(__builtin_bit_cast(s4, r.h));
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = gelu_erf(v[j]);
-        } else if constexpr (FMT == 2) v = unpack_bf16(__builtin_bit_cast(s4, r.h));
-        else if constexpr (FMT == 3) v = unpack_h16(__builtin_bit_cast(s4, r.h));
+        } else if constexpr (FMT == FMT_BF16) v = unpack_bf16(__builtin_bit_cast(s4, r.h));
+        else if constexpr (FMT == FMT_F16) v = unpack_h16(__builtin_bit_cast(s4, r.h));
         else v = r.v;
         if constexpr (LN) v = (v - st.mean) * st.rstd * rk.g + rk.b;
         if constexpr (KS) v = v * rk.s;
@@ -131,12 +152,12 @@ struct ALRowsM : ALRows {
     }
     __device__ __forceinline__ f4 fin(const St& st, const Raw& r) const {
         f4 v;
-        if constexpr (FMT == 1) {
+        if constexpr (FMT == FMT_F16PRE) {
             v = unpack_h16(__builtin_bit_cast(s4, r.h));
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = gelu_erf(v[j]);
-        } else if constexpr (FMT == 2) v = unpack_bf16(__builtin_bit_cast(s4, r.h));
-        else if constexpr (FMT == 3) v = unpack_h16(__builtin_bit_cast(s4, r.h));
+        } else if constexpr (FMT == FMT_BF16) v = unpack_bf16(__builtin_bit_cast(s4, r.h));
+        else if constexpr (FMT == FMT_F16) v = unpack_h16(__builtin_bit_cast(s4, r.h));
         else v = r.v;
         if constexpr (LN) v = (v - st.mean) * st.rstd * r.g + r.b;
         if constexpr (KS) v = v * r.s;
@@ -502,8 +523,8 @@ struct EpStore {
     int act; int accumulate;
     int N;
     const float* addsrc;            // optional [M][ld]: out = addsrc + value (second gradient source of a residual branch; not with nsplit / accumulate)
-    int out_fmt;                    // row epilogue only (run_rows): 0 = fp32 out; 1 = out holds fp16 (clamped), 2 = bf16 -- the 16-bit tensors of
-    int aux_fmt;                    // precision mode bf16 (MLP hidden pre-activation, qkv, du); aux_fmt 1: aux is an fp16 pre-activation
+    int out_fmt;                    // RowFmt, row epilogue only (run_rows): FMT_F32, FMT_F16PRE (fp16, clamped) or FMT_BF16 -- the 16-bit tensors of
+    int aux_fmt;                    // precision mode bf16 (MLP hidden pre-activation, qkv, du); aux_fmt FMT_F16PRE: aux is an fp16 pre-activation
     int rm_Q, rm_H, rm_W;           // rm_Q > 0: GEMM rows are parity-class ordered (ALConvT2) -> remap to pixel rows of the [B,H,W] map
     __device__ __forceinline__ long maprow(int row) const {
         if (rm_Q <= 0) return row;
@@ -628,10 +649,10 @@ struct EpStore {
     static constexpr int kFastModes = 6;
     __device__ __forceinline__ int fast_mode() const {
         const bool gg = act == ACT_MUL_GELU_GRAD, st = colstats || colsum;
-        return (nsplit != 0 || accumulate || rm_Q > 0 || !(act == ACT_NONE || (gg && aux_fmt == 1))) ? 0
-               : st ? ((!gg && out_fmt == 0 && !addsrc) ? 6 : 0)
-               : gg ? ((out_fmt == 2 && !addsrc) ? 5 : 0)
-               : out_fmt == 0 ? (addsrc ? 2 : 1) : (addsrc ? 0 : out_fmt == 1 ? 3 : 4);
+        return (nsplit != 0 || accumulate || rm_Q > 0 || !(act == ACT_NONE || (gg && aux_fmt == FMT_F16PRE))) ? 0
+               : st ? ((!gg && out_fmt == FMT_F32 && !addsrc) ? 6 : 0)
+               : gg ? ((out_fmt == FMT_BF16 && !addsrc) ? 5 : 0)
+               : out_fmt == FMT_F32 ? (addsrc ? 2 : 1) : (addsrc ? 0 : out_fmt == FMT_F16PRE ? 3 : 4);
     }
     template <int MODE, int NT, class BL>
     __device__ __forceinline__ RowPre prefetch_full(const BL&, int, int, int) const { return RowPre{}; }
@@ -695,7 +716,7 @@ struct EpStore {
             }
             if (out_fmt) {                                      // 16-bit primary output (no split / accumulate / dual store in this mode)
                 unsigned short* pp = reinterpret_cast<unsigned short*>(out) + row * ld + n;
-                *reinterpret_cast<s4*>(pp) = out_fmt == 1 ? pack_h16(v) : pack_bf16(v);
+                *reinterpret_cast<s4*>(pp) = out_fmt == FMT_F16PRE ? pack_h16(v) : pack_bf16(v);
             } else if (nsplit > 0 && n >= nsplit) {
                 float* pp = out2 + row * ld2 + (n - nsplit);
                 if (accumulate) v += ld4(pp);
@@ -1282,16 +1303,16 @@ static inline int launch_gemm_lds(const ALRows& al, const BL& bl, const EP& ep, 
                              return ntw == 3 ? launch_gemm_wide<3>(am, bl, ep, M, K, bl.N, s) : launch_gemm_wide<4>(am, bl, ep, M, K, bl.N, s); }
             constexpr bool rows = std::is_same<BL, BLRows>::value, store = std::is_same<EP, EpStore>::value;
             if constexpr (rows && store) {                  // LN -> qkv / fc1, plain x projection of the ConvLSTM
-                if (al.fmt == 0 && !ln && !ks) LEOD_WIDE(0, false, false)
-                if (al.fmt == 0 && ln && !ks) LEOD_WIDE(0, true, false)
+                if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
+                if (al.fmt == FMT_F32 && ln && !ks) LEOD_WIDE(FMT_F32, true, false)
             } else if constexpr (rows && !store) {          // proj / fc2 + LayerScale + residual (fc2: gelu of the fp16 pre-activation)
-                if (al.fmt == 0 && !ln && !ks) LEOD_WIDE(0, false, false)
-                if (al.fmt == 1 && !ln && !ks) LEOD_WIDE(1, false, false)
-                if (al.fmt == 3 && !ln && !ks) LEOD_WIDE(3, false, false)
+                if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
+                if (al.fmt == FMT_F16PRE && !ln && !ks) LEOD_WIDE(FMT_F16PRE, false, false)
+                if (al.fmt == FMT_F16 && !ln && !ks) LEOD_WIDE(FMT_F16, false, false)
             } else if constexpr (!rows && store) {          // dgrads: fp32 / bf16 gradient rows, optional LayerScale factor
-                if (al.fmt == 0 && !ln && !ks) LEOD_WIDE(0, false, false)
-                if (al.fmt == 0 && !ln && ks) LEOD_WIDE(0, false, true)
-                if (al.fmt == 2 && !ln && !ks) LEOD_WIDE(2, false, false)
+                if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
+                if (al.fmt == FMT_F32 && !ln && ks) LEOD_WIDE(FMT_F32, false, true)
+                if (al.fmt == FMT_BF16 && !ln && !ks) LEOD_WIDE(FMT_BF16, false, false)
             }
 #undef LEOD_WIDE
         }
@@ -1300,13 +1321,13 @@ static inline int launch_gemm_lds(const ALRows& al, const BL& bl, const EP& ep, 
         const bool ln = al.ln_w != nullptr, ks = al.kscale != nullptr;
         if (two_phase && !(K & 3) && K >= 4 && (!ln || al.stats_in)) {
 #define LEOD_ALM(F, L, S) { ALRowsM<F, L, S> am; static_cast<ALRows&>(am) = al; return launch_gemm_lds_rw<NT, 1>(am, bl, ep, M, K, nblocks_n, s); }
-            if (al.fmt == 0 && !ln && !ks) LEOD_ALM(0, false, false)
-            if (al.fmt == 0 && ln && !ks) LEOD_ALM(0, true, false)
-            if (al.fmt == 0 && !ln && ks) LEOD_ALM(0, false, true)
-            if (al.fmt == 2 && !ln && !ks) LEOD_ALM(2, false, false)
-            if (al.fmt == 2 && !ln && ks) LEOD_ALM(2, false, true)
-            if (al.fmt == 1 && !ln && !ks) LEOD_ALM(1, false, false)
-            if (al.fmt == 3 && !ln && !ks) LEOD_ALM(3, false, false)
+            if (al.fmt == FMT_F32 && !ln && !ks) LEOD_ALM(FMT_F32, false, false)
+            if (al.fmt == FMT_F32 && ln && !ks) LEOD_ALM(FMT_F32, true, false)
+            if (al.fmt == FMT_F32 && !ln && ks) LEOD_ALM(FMT_F32, false, true)
+            if (al.fmt == FMT_BF16 && !ln && !ks) LEOD_ALM(FMT_BF16, false, false)
+            if (al.fmt == FMT_BF16 && !ln && ks) LEOD_ALM(FMT_BF16, false, true)
+            if (al.fmt == FMT_F16PRE && !ln && !ks) LEOD_ALM(FMT_F16PRE, false, false)
+            if (al.fmt == FMT_F16 && !ln && !ks) LEOD_ALM(FMT_F16, false, false)
 #undef LEOD_ALM
         }
     }
@@ -1323,16 +1344,16 @@ static inline bool use_gemm_lds(int M, int nblocks_n) { return (long)cdiv(M, 64)
 struct XRows {                      // X(m,k) = x[m][k], optional LayerNorm with saved (mean, rstd)
     const float* x; long ld; const float* stats; const float* ln_w; const float* ln_b;
     const float* x2; long ld2; int K1;          // optional concat source for k >= K1
-    int fmt;                                    // 1: x is an fp16 pre-activation, X = gelu(x) (see ALRows::fmt); 2: x holds bf16 rows; 3: fp16 rows
+    int fmt;                                    // RowFmt of x (FMT_F16PRE: X = gelu(x)); hosts set it with set_mode(), never directly
     __device__ __forceinline__ float get(int m, int k) const {
-        if (fmt == 1) return gelu_erf(unpack_h16_1(reinterpret_cast<const unsigned short*>(x)[(long)m * ld + k]));
+        if (fmt == FMT_F16PRE) return gelu_erf(unpack_h16_1(reinterpret_cast<const unsigned short*>(x)[(long)m * ld + k]));
         if (x2 && k >= K1) return x2[(long)m * ld2 + (k - K1)];
         float v = x[(long)m * ld + k];
         if (stats) v = (v - stats[2 * (long)m]) * stats[2 * (long)m + 1] * ln_w[k] + ln_b[k];
         return v;
     }
     __device__ __forceinline__ f4 get4(int m, int k) const {      // k % 4 == 0; K1 % 4 == 0
-        if (fmt == 1) {
+        if (fmt == FMT_F16PRE) {
             f4 v = unpack_h16(*reinterpret_cast<const s4*>(reinterpret_cast<const unsigned short*>(x) + (long)m * ld + k));
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = gelu_erf(v[j]);
@@ -1347,25 +1368,29 @@ struct XRows {                      // X(m,k) = x[m][k], optional LayerNorm with
     // in LayerNorm mode) -- nothing consumes a loaded value here, so all loads of a chunk are in flight together; fin4 applies
     // get4's arithmetic later (same operations in the same order: bit-identical values).  The caller clamps (m, k) to valid
     // coordinates and masks the result.
-    // XM: 0 plain rows (optionally [x | x2]), 1 LayerNorm(x) with saved statistics, 2 gelu(fp16 pre-activation) -- chosen once per
-    // launch (x_mode), so the loop has no mode branches
+    // XM (XMode): XM_ROWS plain rows (optionally [x | x2]), XM_LN LayerNorm(x) with saved statistics, XM_GELU16 gelu(fp16 pre-activation)
+    // -- chosen once per launch (x_mode), so the loop has no mode branches
     template <int XM> __device__ __forceinline__ void raw4(int m, int k, f4& v, u2_& h, f2_& st) const {
-        if constexpr (XM == 2) { h = *reinterpret_cast<const u2_*>(reinterpret_cast<const unsigned short*>(x) + (long)m * ld + k); return; }
-        if constexpr (XM == 1) st = *reinterpret_cast<const f2_*>(stats + 2 * (long)m);
+        if constexpr (XM == XM_GELU16) { h = *reinterpret_cast<const u2_*>(reinterpret_cast<const unsigned short*>(x) + (long)m * ld + k); return; }
+        if constexpr (XM == XM_LN) st = *reinterpret_cast<const f2_*>(stats + 2 * (long)m);
         const float* p = (x2 && k >= K1) ? x2 + (long)m * ld2 + (k - K1) : x + (long)m * ld + k;
         v = ld4(p);
     }
     template <int XM> __device__ __forceinline__ f4 fin4(f4 v, u2_ h, f2_ st, int k, f4 g, f4 b) const {
-        if constexpr (XM == 2) {
+        if constexpr (XM == XM_GELU16) {
             f4 o = unpack_h16(__builtin_bit_cast(s4, h));
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = gelu_erf(o[j]);
             return o;
         }
-        if constexpr (XM == 1) { const f4 n = (v - st.x) * st.y * g + b; return (x2 && k >= K1) ? v : n; }
+        if constexpr (XM == XM_LN) { const f4 n = (v - st.x) * st.y * g + b; return (x2 && k >= K1) ? v : n; }
         return v;
     }
-    int x_mode() const { return fmt == 3 ? 4 : fmt == 2 ? 3 : fmt == 1 ? 2 : (stats ? 1 : 0); }    // 3 / 4: bf16 / fp16 rows (wgrad_wide_bf16_kernel only)
+    // The X mode <-> (fmt, stats) -- these two functions are the only place that knows how the struct holds it (its layout is a kernel
+    // argument).  XM_LN needs stats / ln_w / ln_b set, the other modes need stats == NULL.  XM_BF16 / XM_F16: the bf16-MFMA kernels only
+    // (wgrad_bf16.hpp, wgrad_dma.hpp).
+    void set_mode(int xm) { fmt = xm == XM_GELU16 ? FMT_F16PRE : xm == XM_BF16 ? FMT_BF16 : xm == XM_F16 ? FMT_F16 : FMT_F32; }
+    int x_mode() const { return fmt == FMT_F16 ? XM_F16 : fmt == FMT_BF16 ? XM_BF16 : fmt == FMT_F16PRE ? XM_GELU16 : (stats ? XM_LN : XM_ROWS); }
     __device__ __forceinline__ long waddr(int n, int k, long ldw) const { return (long)n * ldw + k; }
 };
 // loaders with the raw4 / fin4 pair (see XRows) are staged in two phases by wgradw_kernel
@@ -1684,7 +1709,7 @@ __global__ __launch_bounds__(256 * NG, 4) void wgradw_kernel(const float* __rest
 #pragma unroll
     for (int e = 0; e < RK; ++e) kcc[e] = kok[e] ? kc[e] : 0;      // (the raw registers stay uninitialised: each is written and read under the same
                                                                     // workgroup-uniform mode test, and an initial value would become a copy behind every load)
-    if constexpr (TP && XM == 1) {
+    if constexpr (TP && XM == XM_LN) {
         for (int c = threadIdx.x; c < 16 * TK; c += 256 * NG) { sln[0][c] = k0 + c < K ? xl.ln_w[k0 + c] : 0.f; sln[1][c] = k0 + c < K ? xl.ln_b[k0 + c] : 0.f; }
         __syncthreads();
     }
@@ -1724,7 +1749,7 @@ __global__ __launch_bounds__(256 * NG, 4) void wgradw_kernel(const float* __rest
 #pragma unroll
         for (int e = 0; e < RK; ++e) {
             f4 g = zero4(), b = zero4();
-            if constexpr (XM == 1) { g = *reinterpret_cast<const f4*>(&sln[0][kcc[e] - k0]); b = *reinterpret_cast<const f4*>(&sln[1][kcc[e] - k0]); }
+            if constexpr (XM == XM_LN) { g = *reinterpret_cast<const f4*>(&sln[0][kcc[e] - k0]); b = *reinterpret_cast<const f4*>(&sln[1][kcc[e] - k0]); }
             const f4 v = xl.template fin4<XM>(rk[e], hk[e], rst[e], kcc[e], g, b);
             rk[e] = (kok[e] && m0 + kr[e] < mend) ? v : zero4();
         }
@@ -1921,11 +1946,11 @@ static inline int launch_wgradw_cfg(const float* dy, long lddy, const XL& xl, fl
     if constexpr (x_two_phase<XL>::value) {                  // one instantiation per (dY format, X mode): no mode branches in the loop
         const int xm = xl.x_mode();
         if (leod_precision() == 1) {
-            if (dyfmt) { if (xm == 2) LEOD_WGRADW_GO(true, 1, 2); else if (xm == 1) LEOD_WGRADW_GO(true, 1, 1); else LEOD_WGRADW_GO(true, 1, 0); }
-            else { if (xm == 2) LEOD_WGRADW_GO(true, 0, 2); else if (xm == 1) LEOD_WGRADW_GO(true, 0, 1); else LEOD_WGRADW_GO(true, 0, 0); }
+            if (dyfmt) { if (xm == XM_GELU16) LEOD_WGRADW_GO(true, 1, XM_GELU16); else if (xm == XM_LN) LEOD_WGRADW_GO(true, 1, XM_LN); else LEOD_WGRADW_GO(true, 1, XM_ROWS); }
+            else { if (xm == XM_GELU16) LEOD_WGRADW_GO(true, 0, XM_GELU16); else if (xm == XM_LN) LEOD_WGRADW_GO(true, 0, XM_LN); else LEOD_WGRADW_GO(true, 0, XM_ROWS); }
         } else {
-            if (dyfmt || xm == 2) return LEOD_ERR_ARG;       // 16-bit tensors exist in precision mode bf16 only
-            if (xm == 1) LEOD_WGRADW_GO(false, 0, 1); else LEOD_WGRADW_GO(false, 0, 0);
+            if (dyfmt || xm == XM_GELU16) return LEOD_ERR_ARG;       // 16-bit tensors exist in precision mode bf16 only
+            if (xm == XM_LN) LEOD_WGRADW_GO(false, 0, XM_LN); else LEOD_WGRADW_GO(false, 0, XM_ROWS);
         }
     } else {                                                 // gather loaders (conv / stem): one row group
         if (leod_precision() == 1) go(integral_constant<bool, true>{}, integral_constant<int, -1>{}, integral_constant<int, 0>{}, integral_constant<int, 1>{});
@@ -1947,7 +1972,7 @@ static inline int launch_wgradw(const float* dy, long lddy, const XL& xl, float*
     // stage 2 are indifferent or slower
     static const int rc32_on = 1;
     bool rc32 = false;
-    if constexpr (x_two_phase<XL>::value) rc32 = rc32_on && M <= 65536 && xl.x_mode() != 1 && leod_precision() == 1;
+    if constexpr (x_two_phase<XL>::value) rc32 = rc32_on && M <= 65536 && xl.x_mode() != XM_LN && leod_precision() == 1;
     if (K <= 48) return launch_wgradw_cfg<12, 3, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
     if (N <= 48) return launch_wgradw_cfg<3, 12, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
     if (rc32) return launch_wgradw_cfg<6, 6, 3, 3, 32>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);

@@ -20,7 +20,7 @@ LEOD_API int leod_ln_linear_gelu16_fwd(const float* x, const float* ln_w, const 
     const int slab = rowstream_slab(M, N, K);
     static const int gen16 = 1;
     if (!on || leod_precision() != 1) return LEOD_ERR_UNSUPPORTED;
-    if (!slab) return gen16 ? ln_linear_16_generic(x, ln_w, ln_b, eps, W, bias, u16, stats_out, M, N, K, 1, stream) : LEOD_ERR_UNSUPPORTED;
+    if (!slab) return gen16 ? ln_linear_16_generic(x, ln_w, ln_b, eps, W, bias, u16, stats_out, M, N, K, FMT_F16PRE, stream) : LEOD_ERR_UNSUPPORTED;
     const int slabs = N / (16 * slab);
 #define U16_CASE(KCV, NTTV)                                                                                                          \
     if (K == 16 * KCV && slab == NTTV) {                                                                                             \
@@ -36,7 +36,7 @@ LEOD_API int leod_ln_linear_gelu16_fwd(const float* x, const float* ln_w, const 
 }
 
 // Generic 16-bit producers (round 3: stages 3-4 and every geometry the row-streaming kernels do not cover): the LDS-staged / wide-tile
-// GEMMs with a 16-bit row epilogue.  out_fmt 1 = fp16 (the MLP hidden pre-activation), 2 = bf16 (qkv).  ln_w may be NULL (plain rows).
+// GEMMs with a 16-bit row epilogue.  out_fmt FMT_F16PRE = fp16 (the MLP hidden pre-activation), FMT_BF16 = bf16 (qkv).  ln_w may be NULL (plain rows).
 static int ln_linear_16_generic(const float* x, const float* ln_w, const float* ln_b, float eps, const float* W, const float* bias,
                                 void* out16, float* stats_out, int M, int N, int K, int out_fmt, hipStream_t stream) {
     if (leod_precision() != 1 || (K & 3) || (N & 3) || (ln_w && !stats_out)) return LEOD_ERR_UNSUPPORTED;
@@ -60,7 +60,7 @@ LEOD_API int leod_ln_linear_bf16_fwd(const float* x, const float* ln_w, const fl
     static const int gen16 = 1;
     if (leod_precision() != 1) return LEOD_ERR_UNSUPPORTED;
     // the stored rows are the attention kernels' MFMA operands: bf16, or fp16 in precision mode 16f
-    if (!slab) return gen16 ? ln_linear_16_generic(x, ln_w, ln_b, eps, W, bias, out16, stats_out, M, N, K, leod_opfmt() == 2 ? 1 : 2, stream) : LEOD_ERR_UNSUPPORTED;
+    if (!slab) return gen16 ? ln_linear_16_generic(x, ln_w, ln_b, eps, W, bias, out16, stats_out, M, N, K, leod_opfmt() == 2 ? FMT_F16PRE : FMT_BF16, stream) : LEOD_ERR_UNSUPPORTED;
     const int slabs = N / (16 * slab);
 #define O16_CASE(KCV, NTTV)                                                                                                          \
     if (K == 16 * KCV && slab == NTTV) {                                                                                             \
@@ -80,7 +80,7 @@ LEOD_API int leod_linear_lsres_bf16_fwd(const void* a16, const float* W, const f
                                         float* out, int M, int N, int K, hipStream_t stream) {
     LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
     if (!a16 || !W || !res || !out || (K & 7) || leod_precision() != 1) return LEOD_ERR_ARG;
-    ALRows al{}; al.x = reinterpret_cast<const float*>(a16); al.ld = K; al.K = K; al.fmt = leod_opfmt() == 2 ? 3 : 2;   // bf16 rows | fp16 rows (mode 16f)
+    ALRows al{}; al.x = reinterpret_cast<const float*>(a16); al.ld = K; al.K = K; al.fmt = leod_opfmt() == 2 ? FMT_F16 : FMT_BF16;   // bf16 rows | fp16 rows (mode 16f)
     EpLsRes ep{out, nullptr, res, bias, gamma, (long)N, N};
     const int nt = pick_nt(N);
     if (!use_gemm_lds(M, cdiv(N, 16 * nt))) return LEOD_ERR_UNSUPPORTED;
@@ -107,7 +107,7 @@ LEOD_API int leod_linear_lsres_gelu16_fwd(const void* u16, const float* W, const
         });
         return leod_launch_status();
     }
-    ALRows al{}; al.x = a; al.ld = K; al.K = K; al.fmt = 1;
+    ALRows al{}; al.x = a; al.ld = K; al.K = K; al.fmt = FMT_F16PRE;
     EpLsRes ep{out, nullptr, res, bias, gamma, (long)N, N};
     const int nt = pick_nt(N);
     int rc = LEOD_OK;

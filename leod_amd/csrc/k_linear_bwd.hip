@@ -2,22 +2,22 @@
 // C-ABI declared in include/leod_hip.h.
 #include "linear_common.hpp"
 
-// dx[M,K] (=|+=) (dy[M,N] * kscale[N]) @ W[N,K]          (dgrad of y = x W^T)
+// dx[M,K] (=|+=) (dy[M,N] * kscale[N]) @ W[N,K]          (dgrad of y = x W^T).  dy_fmt: 0 fp32 rows, 1 bf16 rows; dx_fmt: 0 fp32, 1 dx is
+// written as bf16 rows (row-epilogue kernels only)
 //   aux_u != NULL : dx *= gelu'(aux_u[M,K])                (through GELU, maxvit.py:107)
 //   nsplit > 0    : columns >= nsplit go to dx2[M, K-nsplit] (ConvLSTM: [dx | dh_prev])
 //   colsum != NULL: colsum[K] += column sums of the stored dx (bias gradient of the producer)
 LEOD_API int leod_linear_dgrad(const float* dy, long lddy, const float* kscale, const float* W, float* dx, long lddx,
                                float* dx2, long lddx2, int nsplit, const float* aux_u, float* colsum,
-                               int accumulate, const float* dres, int M, int N, int K, int dy_bf16, hipStream_t stream) {
-    if (!dy || !W || !dx || (N & 3) || (lddy & 3)) return LEOD_ERR_ARG;
-    const bool out16 = (dy_bf16 & 2) != 0;          // bit 1: dx is written as bf16 rows (row-epilogue kernels only)
-    dy_bf16 &= 1;
-    ALRows al{}; al.x = dy; al.ld = lddy; al.kscale = kscale; al.K = N; al.fmt = dy_bf16 ? 2 : 0;
+                               int accumulate, const float* dres, int M, int N, int K, int dy_fmt, int dx_fmt, hipStream_t stream) {
+    if (!dy || !W || !dx || (N & 3) || (lddy & 3) || (dy_fmt != 0 && dy_fmt != 1) || (dx_fmt != 0 && dx_fmt != 1)) return LEOD_ERR_ARG;
+    const bool dy_bf16 = dy_fmt != 0, out16 = dx_fmt != 0;
+    ALRows al{}; al.x = dy; al.ld = lddy; al.kscale = kscale; al.K = N; al.fmt = dy_bf16 ? FMT_BF16 : FMT_F32;
     EpStore ep = ep_store(dx, lddx, K);
     if (out16) {
         if (leod_precision() != 1 || dx2 || colsum || accumulate || dres || aux_u || nsplit > 0 || (K & 3) || !use_gemm_lds(M, cdiv(K, 16 * pick_nt(K))))
             return LEOD_ERR_UNSUPPORTED;
-        ep.out_fmt = 2;
+        ep.out_fmt = FMT_BF16;
     }
     ep.out2 = dx2; ep.ld2 = lddx2; ep.nsplit = nsplit; ep.accumulate = accumulate; ep.colsum = colsum; ep.addsrc = dres;
     if (dres && (nsplit > 0 || accumulate)) return LEOD_ERR_ARG;
@@ -81,12 +81,11 @@ LEOD_API int leod_linear_dgrad_gelu16(const float* dy, const float* kscale, cons
     const int slab = rowstream_slab(M, K, N);
     if (!slab) {
         // generic shapes (stages 3-4): LDS-staged / wide-tile dgrad, gelu'(fp16 u) and the 16-bit store in the row epilogue
-        static const int gen16 = 1;
         const int nt = pick_nt(K);
-        if (!gen16 || (N & 3) || (K & 3) || !use_gemm_lds(M, cdiv(K, 16 * nt))) return LEOD_ERR_UNSUPPORTED;
+        if ((N & 3) || (K & 3) || !use_gemm_lds(M, cdiv(K, 16 * nt))) return LEOD_ERR_UNSUPPORTED;
         ALRows al{}; al.x = dy; al.ld = N; al.kscale = kscale; al.K = N;
         EpStore ep = ep_store(reinterpret_cast<float*>(dx), K, K);
-        ep.act = ACT_MUL_GELU_GRAD; ep.aux = reinterpret_cast<const float*>(u16); ep.ldaux = K; ep.aux_fmt = 1; ep.out_fmt = out_bf16 ? 2 : 0;
+        ep.act = ACT_MUL_GELU_GRAD; ep.aux = reinterpret_cast<const float*>(u16); ep.ldaux = K; ep.aux_fmt = FMT_F16PRE; ep.out_fmt = out_bf16 ? FMT_BF16 : FMT_F32;
         int rc = LEOD_OK;
         DISPATCH_NT(nt, { BLTrans bl{W, (long)K, K, NT}; rc = launch_gemm_lds<NT>(al, bl, ep, M, N, cdiv(K, 16 * NT), stream); });
         return rc;

@@ -56,7 +56,7 @@ constexpr int wgw_lds_bytes() {
 }
 
 // TN x TK: 16 x 16 tiles of the workgroup's dW tile; NWN x NWK: wave grid over it (each wave 3 x 3 tiles; waves left over split the
-// 32-row steps of a chunk); RC rows per chunk; DYF: dY fp32 (0) / bf16 (1); XM: see XRows (0 rows, 1 LayerNorm, 2 gelu(fp16), 3 bf16 rows, 4 fp16 rows)
+// 32-row steps of a chunk); RC rows per chunk; DYF: dY fp32 (0) / bf16 (1); XM: the XMode of X (gemm16.hpp)
 template <int TN, int TK, int NWN, int NWK, int RC, int DYF, int XM, int OCC>
 __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* __restrict__ dyv, long lddy, XRows xl, float* dW, long ldw,
                                                                     float* dbias, f4* __restrict__ part, int M, int N, int K, int dbg) {
@@ -70,12 +70,12 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
     static_assert((WA == 3 || WA == 6) && (WB == 3 || WB == 6) && WA * WB <= 18 && NWN * NWK * MS == 4 && (RC / 16) % MS == 0 &&
                   (MS == 1 || (WA == 3 && WB == 3)), "4 waves of 3 x 3, 6 x 3 or 3 x 6 tiles");
     constexpr int BST = 16 * 16 + 16;
-    constexpr int DCW = DYF ? 8 : 4, XCW = XM >= 2 ? 8 : 4;                 // columns per 16-byte load
+    constexpr int DCW = DYF ? 8 : 4, XCW = XM >= XM_GELU16 ? 8 : 4;                 // columns per 16-byte load
     constexpr int DSPR = 16 * TN / DCW, XSPR = 16 * TK / XCW;
     constexpr int DRG = wgw_row_groups(DSPR) < RC ? wgw_row_groups(DSPR) : RC, XRG = wgw_row_groups(XSPR) < RC ? wgw_row_groups(XSPR) : RC;
     // XG (gelu operands): the evaluation is VALU-bound, so ALL four waves stage X -- slot s = tid + 256 e of the chunk's RC x XSPR slots
     // (row s / XSPR, column slot s % XSPR; offsets per slot in registers) instead of three waves with a fixed column
-    constexpr bool XG = XM == 2;
+    constexpr bool XG = XM == XM_GELU16;
     static_assert(!XG || (RC * XSPR) % 256 == 0, "whole slots per thread");
     constexpr int RN = RC / DRG, RK = XG ? RC * XSPR / 256 : RC / XRG;
     constexpr int SDY = (RC / 16) * TN * BST, SX = (RC / 16) * TK * BST;    // bf16 elements of one buffer
@@ -100,9 +100,9 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
     }
     const char* xbase; long xstride;
     {
-        constexpr int ES = XM >= 2 ? 2 : 4;
+        constexpr int ES = XM >= XM_GELU16 ? 2 : 4;
         const int c = xok ? xcol : 0;
-        if (XM == 0 && xl.x2 && c >= xl.K1) { xbase = reinterpret_cast<const char*>(xl.x2) + (long)(c - xl.K1) * ES; xstride = xl.ld2 * ES; }
+        if (XM == XM_ROWS && xl.x2 && c >= xl.K1) { xbase = reinterpret_cast<const char*>(xl.x2) + (long)(c - xl.K1) * ES; xstride = xl.ld2 * ES; }
         else { xbase = reinterpret_cast<const char*>(xl.x) + (long)c * ES; xstride = xl.ld * ES; }
     }
     const int dl0 = ((drg >> 4) * TN + ((dcs * DCW) >> 4)) * BST + (drg & 15) * 16 + ((dcs * DCW) & 15);
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
         }
     }
     u4_ rd[RN], rx[RK];
-    f2_ rst[XM == 1 ? RK : 1];
+    f2_ rst[XM == XM_LN ? RK : 1];
     auto fetch = [&](long m0, auto tailc) {
         constexpr bool TAIL = decltype(tailc)::value;
         if (dact) {
@@ -144,10 +144,10 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
                 if constexpr (TAIL) {
                     const long r = min(m0 + xrg + XRG * e, (long)M - 1);
                     rx[e] = *reinterpret_cast<const u4_*>(xbase + r * xstride);
-                    if constexpr (XM == 1) rst[e] = *reinterpret_cast<const f2_*>(xl.stats + 2 * r);
+                    if constexpr (XM == XM_LN) rst[e] = *reinterpret_cast<const f2_*>(xl.stats + 2 * r);
                 } else {
                     rx[e] = *reinterpret_cast<const u4_*>(p + (long)(XRG * e) * xstride);
-                    if constexpr (XM == 1) rst[e] = *reinterpret_cast<const f2_*>(xl.stats + 2 * (m0 + xrg + XRG * e));
+                    if constexpr (XM == XM_LN) rst[e] = *reinterpret_cast<const f2_*>(xl.stats + 2 * (m0 + xrg + XRG * e));
                 }
             }
         }
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
 #pragma unroll
             for (int e = 0; e < RK; ++e) {
                 const bool ok = XG ? (gxk[e] && gxr[e] < lim) : (xok && xrg + XRG * e < lim);
-                if constexpr (XM == 2) {
+                if constexpr (XM == XM_GELU16) {
                     auto cv = [&](unsigned w) -> unsigned {          // two fp16 pre-activations -> two bf16 gelu values
                         const h2_ h = __builtin_bit_cast(h2_, w);
                         const f2_ u = {(float)h.x, (float)h.y};
@@ -185,12 +185,12 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
                     };
                     const u4_ o = {cv(rx[e].x), cv(rx[e].y), cv(rx[e].z), cv(rx[e].w)};
                     *reinterpret_cast<u4_*>(d + gxo[e]) = o;
-                } else if constexpr (XM == 3) {                     // bf16 rows: staged as loaded
+                } else if constexpr (XM == XM_BF16) {                     // bf16 rows: staged as loaded
                     u4_ v = rx[e];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = ok ? v[j] : 0u;
                     *reinterpret_cast<u4_*>(d + wgw_slot_off<XRG, TK, BST>(e)) = v;
-                } else if constexpr (XM == 4) {                     // fp16 rows (precision mode 16f: the attention output): re-rounded to bf16
+                } else if constexpr (XM == XM_F16) {                     // fp16 rows (precision mode 16f: the attention output): re-rounded to bf16
                     auto cv = [&](unsigned w) -> unsigned {          // two fp16 values -> two bf16 values
                         const h2_ h = __builtin_bit_cast(h2_, w);
                         return ok ? pack_bf16x2(f2_{(float)h.x, (float)h.y}) : 0u;
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
                     *reinterpret_cast<u4_*>(d + wgw_slot_off<XRG, TK, BST>(e)) = o;
                 } else {
                     f4 v = __builtin_bit_cast(f4, rx[e]);
-                    if constexpr (XM == 1) v = (v - rst[e].x) * rst[e].y;
+                    if constexpr (XM == XM_LN) v = (v - rst[e].x) * rst[e].y;
                     u2_ o = {pack_bf16x2(f2_{v.x, v.y}), pack_bf16x2(f2_{v.z, v.w})};
                     o.x = ok ? o.x : 0u; o.y = ok ? o.y : 0u;
                     *reinterpret_cast<u2_*>(d + wgw_slot_off<XRG, TK, BST>(e)) = o;
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
     };
     // ---- accumulators: 3 x 3 tiles of dW and the column sums of dY (bias gradient; LayerNorm shift term) ----------------------------
     // bias tile a of a wave's three: every wave needs its own in LayerNorm mode; otherwise the waves of a row of the grid share them out
-    const bool bias_any = XM == 1 || (dbias != nullptr && blockIdx.z == 0);
+    const bool bias_any = XM == XM_LN || (dbias != nullptr && blockIdx.z == 0);
     f4 acc[WA][WB], bacc[WA];
 #pragma unroll
     for (int a = 0; a < WA; ++a) {
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
                 if (bias_any) {
 #pragma unroll
                     for (int a = 0; a < WA; ++a)
-                        if (XM == 1 || a % NWK == wk) bacc[a] = mfma16_bf16(pa[a], ones4, bacc[a]);
+                        if (XM == XM_LN || a % NWK == wk) bacc[a] = mfma16_bf16(pa[a], ones4, bacc[a]);
                 }
             }
         } else {
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
             if (bias_any) {
 #pragma unroll
                 for (int a = 0; a < WA; ++a)
-                    if (XM == 1 || a % NWK == wk) bacc[a] = mfma32_bf16(pa[a], ones, bacc[a]);
+                    if (XM == XM_LN || a % NWK == wk) bacc[a] = mfma32_bf16(pa[a], ones, bacc[a]);
             }
         }
         }
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256, OCC) void wgrad_wide_bf16_kernel(const void* _
     if (dbg & 1) return;
     // ---- epilogue: acc[a][b][r] = tile element (n = 4q + r, k = i); bacc[a][r] = column sum of dY column n (the same in every lane i) --
     // LayerNorm scale / shift of the finished tile (see the header)
-    if constexpr (XM == 1) {
+    if constexpr (XM == XM_LN) {
 #pragma unroll
         for (int b = 0; b < WB; ++b) {
             const int k = k0 + 16 * (wk * WB + b) + i;
@@ -444,26 +444,22 @@ template <int TN, int TK, int NWN, int NWK, int RC, int DYF, int XM, int OCC>
 static inline int launch_wgrad_wide_cfg(const void* dy, long lddy, const XRows& xl, float* dW, long ldw, float* dbias,
                                         int M, int N, int K, hipStream_t s) {
     constexpr int dbg = 0;          // ablation bits of the kernel (skip epilogue / MFMAs / loads): compile-time, for experiments
-    static const int tune_wgs = OCC * 256;
     constexpr int LDS = wgw_lds_bytes<TN, TK, RC, 4 / (NWN * NWK)>();
     const int tiles = cdiv(N, TN * 16) * cdiv(K, TK * 16), chunks = cdiv(M, RC);
     // all workgroups resident (OCC per CU); >= 2 chunks each; a multiple of 8 per output tile keeps the workgroups that stream the same
     // rows for different tiles on one XCD (see launch_wgradw_cfg)
     // launches of <= 60 k rows (stages 3-4) run beside the main lane's kernels and are latency-bound: 384 workgroups instead of OCC * 256
     // leave wave slots to the other lane and halve the partial tiles (15.84 -> 15.76-15.79 ms per step, profiles/r04_a_graph_ab.txt)
-    static const int tune_small = 384;
-    static const int small_rows = 60000;
-    const int wgs = (tune_small > 0 && M <= small_rows) ? tune_small : tune_wgs;
+    const int wgs = M <= 60000 ? 384 : OCC * 256;
     int gx = max(1, min(chunks / 2, wgs / tiles));
     if (gx >= 16) gx &= ~7;
     dim3 grid(gx, cdiv(N, TN * 16), cdiv(K, TK * 16));
     auto kern = wgrad_wide_bf16_kernel<TN, TK, NWN, NWK, RC, DYF, XM, OCC>;
     static bool attr_set = false;                             // dynamic LDS opt-in, once per instantiation
     if (!attr_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS); attr_set = true; }
-    static const int use_part = 1;
     constexpr int NW = NWN * NWK, NSL = (TN / NWN) * (TK / NWK) + TN / NWN;
     const long O = (long)tiles * NW * NSL * 64;               // f4 per partial
-    f4* part = (use_part && gx > 1) ? wgrad_wide_scratch(s, (size_t)gx * O * sizeof(f4)) : nullptr;
+    f4* part = gx > 1 ? wgrad_wide_scratch(s, (size_t)gx * O * sizeof(f4)) : nullptr;
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, dy, lddy, xl, dW, ldw, dbias, part, M, N, K, dbg);
     if (part != nullptr && !(dbg & 1)) {
         // ~2048 waves of reduce threads: groups of `per` partials
@@ -487,31 +483,30 @@ static inline int launch_wgrad_wide_cfg(const void* dy, long lddy, const XRows& 
 // chunk rows: ~18-25 KB of loads per chunk (fp32 rows carry twice the bytes of 16-bit rows, and twice the staging registers)
 static inline int wgrad_wide_combo(const XRows& xl, int N, int K, int dyfmt) {
     const int xm = xl.x_mode();
-    if (xm == 4) {                                                   // fp32 dY, fp16 rows (mode 16f): the tilings of the bf16-row cases
+    if (xm == XM_F16) {                                              // fp32 dY, fp16 rows (mode 16f): the tilings of the bf16-row cases
         if (dyfmt) return 0;
         if (N <= 48 && K <= 48) return 14;
         if (K <= 48 || N <= 48) return 0;
-        static const int big4 = 1;
-        return (big4 && K % 192 == 0 && N >= 96) ? 16 : 15;
+        return (K % 192 == 0 && N >= 96) ? 16 : 15;
     }
-    const int c = (dyfmt ? 1 : 0) * 4 + xm;        // 0: f32/rows 1: f32/LN 2: f32/gelu16 3: f32/bf16 rows 4: bf16/rows 5: bf16/LN
-    if (c > 5) return 0;
-    if (N <= 48 && K <= 48) return c == 0 ? 1 : c == 3 ? 8 : 0;
-    if (K <= 48) return c == 5 ? 2 : 0;
-    if (N <= 48) return c == 2 ? 3 : 0;
+    // the covered (dY, X) pairs; any other (fp32 dY with LayerNorm, bf16 dY with 16-bit X) returns 0 below
+    const bool f32_rows = !dyfmt && xm == XM_ROWS, f32_gelu = !dyfmt && xm == XM_GELU16, f32_bf16 = !dyfmt && xm == XM_BF16;
+    const bool b16_rows = dyfmt && xm == XM_ROWS, b16_ln = dyfmt && xm == XM_LN;
+    if (N <= 48 && K <= 48) return f32_rows ? 1 : f32_bf16 ? 8 : 0;
+    if (K <= 48) return b16_ln ? 2 : 0;
+    if (N <= 48) return f32_gelu ? 3 : 0;
     // 192-wide tiles along the 16-bit operand's side: 192 x 96 outputs for bf16 dY with fp32 X (qkv, fc1, ConvLSTM), 96 x 192 for fp32 dY
     // with 16-bit X (fc2 on the fp16 hidden, proj on bf16 O)
-    static const int big = 1;
-    if (big && N % 192 == 0 && K >= 96 && (c == 5 || c == 4)) return c == 5 ? 10 : 11;
-    if (big && K % 192 == 0 && N >= 96 && (c == 2 || c == 3)) return c == 2 ? 12 : 13;
-    return c == 0 ? 4 : c == 5 ? 5 : c == 2 ? 6 : c == 4 ? 7 : c == 3 ? 9 : 0;
+    if (N % 192 == 0 && K >= 96 && (b16_ln || b16_rows)) return b16_ln ? 10 : 11;
+    if (K % 192 == 0 && N >= 96 && (f32_gelu || f32_bf16)) return f32_gelu ? 12 : 13;
+    return f32_rows ? 4 : b16_ln ? 5 : f32_gelu ? 6 : b16_rows ? 7 : f32_bf16 ? 9 : 0;
 }
 static inline bool use_wgrad_wide(const XRows& xl, long lddy, int M, int N, int K, int dyfmt) {
     if (leod_precision() != 1 || M < 8192) return false;
     const int xm = xl.x_mode();
-    const int dcw = dyfmt ? 8 : 4, xcw = xm >= 2 ? 8 : 4;
+    const int dcw = dyfmt ? 8 : 4, xcw = xm_is16(xm) ? 8 : 4;
     if ((N % dcw) || (lddy % dcw) || (K % xcw) || (xl.ld % xcw)) return false;
-    if (xl.x2 && (xm != 0 || (xl.K1 % 4) || (xl.ld2 % 4))) return false;
+    if (xl.x2 && (xm != XM_ROWS || (xl.K1 % 4) || (xl.ld2 % 4))) return false;
     return wgrad_wide_combo(xl, N, K, dyfmt) != 0;
 }
 static inline int launch_wgrad_wide(const void* dy, long lddy, const XRows& xl, float* dW, long ldw, float* dbias,
@@ -519,22 +514,22 @@ static inline int launch_wgrad_wide(const void* dy, long lddy, const XRows& xl, 
 #define LEOD_WGW(TN, TK, NWN, NWK, RC, DYF, XM, OCC) \
     return launch_wgrad_wide_cfg<TN, TK, NWN, NWK, RC, DYF, XM, OCC>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s)
     switch (wgrad_wide_combo(xl, N, K, dyfmt)) {
-        case 1: LEOD_WGW(3, 3, 1, 1, 64, 0, 0, 2);
-        case 2: LEOD_WGW(12, 3, 4, 1, 32, 1, 1, 4);
-        case 3: LEOD_WGW(3, 12, 1, 4, 32, 0, 2, 3);
-        case 4: LEOD_WGW(6, 6, 2, 2, 32, 0, 0, 3);
-        case 5: LEOD_WGW(6, 6, 2, 2, 32, 1, 1, 3);
-        case 6: LEOD_WGW(6, 6, 2, 2, 64, 0, 2, 3);
-        case 7: LEOD_WGW(6, 6, 2, 2, 32, 1, 0, 3);
-        case 8: LEOD_WGW(3, 3, 1, 1, 64, 0, 3, 2);
-        case 9: LEOD_WGW(6, 6, 2, 2, 32, 0, 3, 3);
-        case 10: LEOD_WGW(12, 6, 2, 2, 32, 1, 1, 2);
-        case 11: LEOD_WGW(12, 6, 2, 2, 32, 1, 0, 2);
-        case 12: LEOD_WGW(6, 12, 2, 2, 64, 0, 2, 2);
-        case 13: LEOD_WGW(6, 12, 2, 2, 32, 0, 3, 2);
-        case 14: LEOD_WGW(3, 3, 1, 1, 64, 0, 4, 2);
-        case 15: LEOD_WGW(6, 6, 2, 2, 32, 0, 4, 3);
-        case 16: LEOD_WGW(6, 12, 2, 2, 32, 0, 4, 2);
+        case 1: LEOD_WGW(3, 3, 1, 1, 64, 0, XM_ROWS, 2);
+        case 2: LEOD_WGW(12, 3, 4, 1, 32, 1, XM_LN, 4);
+        case 3: LEOD_WGW(3, 12, 1, 4, 32, 0, XM_GELU16, 3);
+        case 4: LEOD_WGW(6, 6, 2, 2, 32, 0, XM_ROWS, 3);
+        case 5: LEOD_WGW(6, 6, 2, 2, 32, 1, XM_LN, 3);
+        case 6: LEOD_WGW(6, 6, 2, 2, 64, 0, XM_GELU16, 3);
+        case 7: LEOD_WGW(6, 6, 2, 2, 32, 1, XM_ROWS, 3);
+        case 8: LEOD_WGW(3, 3, 1, 1, 64, 0, XM_BF16, 2);
+        case 9: LEOD_WGW(6, 6, 2, 2, 32, 0, XM_BF16, 3);
+        case 10: LEOD_WGW(12, 6, 2, 2, 32, 1, XM_LN, 2);
+        case 11: LEOD_WGW(12, 6, 2, 2, 32, 1, XM_ROWS, 2);
+        case 12: LEOD_WGW(6, 12, 2, 2, 64, 0, XM_GELU16, 2);
+        case 13: LEOD_WGW(6, 12, 2, 2, 32, 0, XM_BF16, 2);
+        case 14: LEOD_WGW(3, 3, 1, 1, 64, 0, XM_F16, 2);
+        case 15: LEOD_WGW(6, 6, 2, 2, 32, 0, XM_F16, 3);
+        case 16: LEOD_WGW(6, 12, 2, 2, 32, 0, XM_F16, 2);
     }
 #undef LEOD_WGW
     return LEOD_ERR_UNSUPPORTED;

@@ -21,8 +21,15 @@ struct Prep16 {                 // one operand of wgrad_prep16_kernel
     const float* src2; long ld2; int C1;       // mode 4: columns >= C1 come from src2 (fp32)
     const float* stats;         // mode 1: (mean, rstd) per row
     unsigned short* dst;        // bf16 [M][C]
-    int C, mode;                // mode 0 fp32, 1 LayerNorm xhat of fp32 rows, 2 gelu(fp16), 3 fp16, 4 fp32 [x | x2], -1: nothing to do
+    int C, mode;                // Prep16Mode
 };
+// Prep16::mode is private to the preparation pass and is NOT the XMode: 3 means fp16 rows here (bf16 rows are never prepared), and the
+// concat source, a flag next to the XMode everywhere else, is mode 4.  wgrad_prep16_kernel tests the numbers.
+enum Prep16Mode : int { P16_NONE = -1, P16_F32 = 0, P16_LN = 1 /* xhat of fp32 rows */, P16_GELU16 = 2, P16_F16 = 3, P16_CONCAT = 4 /* fp32 [x | x2] */ };
+static inline int prep16_mode(int xm, bool concat) {
+    if (xm_is_mfma_operand(xm)) return P16_NONE;
+    return xm == XM_LN ? P16_LN : xm == XM_GELU16 ? P16_GELU16 : xm == XM_F16 ? P16_F16 : concat ? P16_CONCAT : P16_F32;
+}
 
 // 8 columns per thread (one 16-byte store); grid (ceil(M * maxC8 / 256), 2, problems): y picks the operand, z the problem of a grouped launch
 struct Prep16Group { Prep16 a[4]; Prep16 b[4]; };
@@ -224,8 +231,8 @@ static inline bool wgrad_dma_ok(const XRows& xl, long lddy, int M, int N, int K,
     if (!T) return false;
     const int xm = xl.x_mode();
     if ((lddy & 7) || (xl.ld & 7)) return false;
-    if (xl.x2 && (xm != 0 || (xl.K1 & 7) || (xl.ld2 & 7))) return false;
-    const size_t need = (size_t)M * ((dyfmt ? 0 : N) + (xm == 3 ? 0 : K)) * 2;
+    if (xl.x2 && (xm != XM_ROWS || (xl.K1 & 7) || (xl.ld2 & 7))) return false;
+    const size_t need = (size_t)M * ((dyfmt ? 0 : N) + (xm_is_mfma_operand(xm) ? 0 : K)) * 2;
     if (need > kWgdOperandBytes) return false;
     // row ranges above these stay on the register-staged wide kernel, which streams at 2-2.9 TB/s there and needs no preparation pass
     // (profiles/r06_f_wgrad_dma_1mpx_kbench.txt: RVT-B 1 Mpx stages 2-4, 338 k / 84 k / 21 k rows, 1262 / 1161 / 1719 us -> 948 / 607 / 419;
@@ -233,7 +240,7 @@ static inline bool wgrad_dma_ok(const XRows& xl, long lddy, int M, int N, int K,
     if (M > (T == 6 ? 60000 : 400000)) return false;
     // the square projections (fp32 dY AND 16-bit attention rows to convert, 4-16 output tiles) stay on the register-staged kernel: the
     // preparation pass is as long as the contraction there (30 vs 36 us at 53 760 x 192 x 192, 27 vs 28 us at 13 440 x 384 x 384)
-    if (!dyfmt && xm != 3 && xm != 2 && (long)N * K < 200000) return false;
+    if (!dyfmt && xm != XM_BF16 && xm != XM_GELU16 && (long)N * K < 200000) return false;
     return true;
 }
 
@@ -316,7 +323,7 @@ static inline int launch_wgrad_dma_group_t(int n, const WgdHostProb* hp, int M, 
         const long O = (long)tiles * NW * NSL * 64;            // f4 per partial
         offs_part[k] = off; off += ((size_t)gx * O * sizeof(f4) + 1023) & ~(size_t)1023;
         offs_a[k] = off; off += h.dyfmt ? 0 : (((size_t)M * h.N * 2 + 1023) & ~(size_t)1023);
-        offs_b[k] = off; off += xm == 3 ? 0 : (((size_t)M * h.K * 2 + 1023) & ~(size_t)1023);
+        offs_b[k] = off; off += xm_is_mfma_operand(xm) ? 0 : (((size_t)M * h.K * 2 + 1023) & ~(size_t)1023);
         g.p[k].cpw = cpw; g.p[k].gx = gx; g.p[k].ny = h.N / TW; g.p[k].nz = h.K / TW; g.p[k].N = h.N; g.p[k].K = h.K; g.p[k].blk0 = blk;
         blk += gx * tiles;
         const int ob = (int)cdiv(O, 256);
@@ -325,7 +332,7 @@ static inline int launch_wgrad_dma_group_t(int n, const WgdHostProb* hp, int M, 
         groups = cdiv(gx, per);
         rg.p[k] = WgrProb{nullptr, h.dW, h.dbias, h.ldw, gx, h.N / TW, h.K / TW, per, h.N, h.K, ob, groups};
         obmax = max(obmax, ob); grmax = max(grmax, groups);
-        any_ln = any_ln || xm == 1;
+        any_ln = any_ln || xm == XM_LN;
     }
     g.n = n;
     char* ws = reinterpret_cast<char*>(wgrad_wide_scratch(s, off + 4096));
@@ -337,22 +344,22 @@ static inline int launch_wgrad_dma_group_t(int n, const WgdHostProb* hp, int M, 
         unsigned short* a16 = reinterpret_cast<unsigned short*>(ws + offs_a[k]);
         unsigned short* b16 = reinterpret_cast<unsigned short*>(ws + offs_b[k]);
         Prep16 pa{}, pb{};
-        pa.mode = pb.mode = -1;
-        if (!h.dyfmt) pa = Prep16{h.dy, h.lddy, nullptr, 0, 0, nullptr, a16, h.N, 0};
-        if (xm != 3) pb = Prep16{h.xl.x, h.xl.ld, h.xl.x2, h.xl.ld2, h.xl.x2 ? h.xl.K1 : h.K, h.xl.stats, b16, h.K,
-                                 xm == 1 ? 1 : xm == 2 ? 2 : xm == 4 ? 3 : (h.xl.x2 ? 4 : 0)};
+        pa.mode = pb.mode = P16_NONE;
+        if (!h.dyfmt) pa = Prep16{h.dy, h.lddy, nullptr, 0, 0, nullptr, a16, h.N, P16_F32};
+        if (!xm_is_mfma_operand(xm)) pb = Prep16{h.xl.x, h.xl.ld, h.xl.x2, h.xl.ld2, h.xl.x2 ? h.xl.K1 : h.K, h.xl.stats, b16, h.K,
+                                                 prep16_mode(xm, h.xl.x2 != nullptr)};
         pg.a[k] = pa; pg.b[k] = pb;
         if (pa.mode >= 0) { any_prep = true; c8max = max(c8max, h.N / 8); }
         if (pb.mode >= 0) { any_prep = true; c8max = max(c8max, h.K / 8); }
         g.p[k].A = h.dyfmt ? reinterpret_cast<const unsigned short*>(h.dy) : a16;
         g.p[k].lda = h.dyfmt ? h.lddy : h.N;
-        g.p[k].B = xm == 3 ? reinterpret_cast<const unsigned short*>(h.xl.x) : b16;
-        g.p[k].ldb = xm == 3 ? h.xl.ld : h.K;
-        g.p[k].ln_w = xm == 1 ? h.xl.ln_w : nullptr; g.p[k].ln_b = xm == 1 ? h.xl.ln_b : nullptr;
+        g.p[k].B = xm_is_mfma_operand(xm) ? reinterpret_cast<const unsigned short*>(h.xl.x) : b16;
+        g.p[k].ldb = xm_is_mfma_operand(xm) ? h.xl.ld : h.K;
+        g.p[k].ln_w = xm == XM_LN ? h.xl.ln_w : nullptr; g.p[k].ln_b = xm == XM_LN ? h.xl.ln_b : nullptr;
         g.p[k].dbias_flag = h.dbias; g.p[k].part = part;
         rg.p[k].part = part;
     }
-    for (int k = n; k < 4; ++k) { pg.a[k].mode = pg.b[k].mode = -1; }
+    for (int k = n; k < 4; ++k) { pg.a[k].mode = pg.b[k].mode = P16_NONE; }
     if (any_prep) hipLaunchKernelGGL(wgrad_prep16_kernel, dim3(cdiv((long)M * c8max, 256), 2, n), dim3(256), 0, s, pg, M);
     if (any_ln) {
         auto kern = wgrad_dma_kernel<T, RC, NS, true>;

@@ -440,7 +440,7 @@ def _linear_dgrad(dy, W, kscale, aux_u, colsum, out, accumulate, split, out2, dr
             out = torch.empty(dy.shape[:-1] + (K,), dtype=torch.bfloat16 if out_bf16 else F32, device=dy.device)
         ld1, ld2 = K, 0
     check(_l().leod_linear_dgrad(_p(dy), N, _p(kscale), _p(W), _p(out), ld1, _p(out2), ld2, split, _p(aux_u),
-                                  _p(colsum), 1 if accumulate else 0, _p(dres), M, N, K, (1 if dy16 else 0) | (2 if out_bf16 else 0), _stream()),
+                                  _p(colsum), 1 if accumulate else 0, _p(dres), M, N, K, 1 if dy16 else 0, 1 if out_bf16 else 0, _stream()),
           'linear_dgrad')
     return (out, out2) if split else out
 
@@ -458,6 +458,24 @@ def _wgrad_workspace(device):
         _WORKSPACES[s] = ws
 
 
+def _x_fmt(x, stats, gelu):
+    """x_fmt of leod_linear_wgrad / leod_linear_wgrad_group."""
+    if gelu:
+        return 2
+    if x.dtype is torch.bfloat16:
+        return 3
+    if x.dtype is torch.float16:
+        return 4
+    return 1 if stats is not None else 0
+
+
+def _wgrad_work(M, N, K, dy16, x16):
+    """(nbytes, flops, nbytes16) of one weight gradient for the probe: the algorithmic work of one launch -- reads dy and X once,
+    read-modify-writes dW once, 2*M*N*K flops; nbytes16: the same with both operands in 16 bits."""
+    return ((2.0 if dy16 else 4.0) * M * N + (2.0 if x16 else 4.0) * M * K + 4.0 * N * K, 2.0 * M * N * K,
+            2.0 * M * (N + K) + 4.0 * N * K)
+
+
 def linear_wgrad(dy, x, dW, dbias=None, stats=None, ln_w=None, ln_b=None, x2=None, x_gelu=None):
     """dW += dy^T X ; dbias += colsum(dy).  X = x | LN(x) | [x|x2] | gelu(x) (x the fp16 pre-activation; x_gelu as in linear_lsres_fwd)."""
     dy16 = dy.dtype is torch.bfloat16
@@ -470,36 +488,18 @@ def linear_wgrad(dy, x, dW, dbias=None, stats=None, ln_w=None, ln_b=None, x2=Non
     K1 = x.shape[-1]
     if M >= 8192 and _stream() not in _WORKSPACES and is_16bit():
         _wgrad_workspace(dW.device)
-    if x.dtype is torch.float16 and x_gelu is not False:     # X = gelu(x): x is the fp16 pre-activation of the MLP hidden
-        _ck(x, torch.float16, 'x')
-        if stats is not None or x2 is not None or dy16:
-            raise LeodHipError('linear_wgrad: LayerNorm / concat / bf16-dy options do not combine with an fp16 pre-activation')
-        ev = _probe('linear_wgrad', 4.0 * (M * N + N * K) + 2.0 * M * K, 2.0 * M * N * K, rows=M, nbytes16=2.0 * M * (N + K) + 4.0 * N * K)
-        check(_l().leod_linear_wgrad_gelu16(_p(dy), N, _p(x), _p(dW), _p(dbias), M, N, K, _stream()), 'linear_wgrad_gelu16')
-        if ev is not None:
-            ev.record()
-        return
+    gelu = x.dtype is torch.float16 and x_gelu is not False   # X = gelu(x): x is the fp16 pre-activation of the MLP hidden
+    if gelu and (stats is not None or x2 is not None or dy16):
+        raise LeodHipError('linear_wgrad: LayerNorm / concat / bf16-dy options do not combine with an fp16 pre-activation')
     x16 = _is16(x)                                            # 16-bit rows (the attention output: bf16, or fp16 in mode 16f)
-    xh = x.dtype is torch.float16
     _ck(x, x.dtype if x16 else F32, 'x')
-    # algorithmic work of one launch: reads dy, X once, read-modify-writes dW once; 2*M*N*K flops
-    ev = _probe('linear_wgrad', (2.0 if dy16 else 4.0) * M * N + (2.0 if x16 else 4.0) * M * K + 4.0 * N * K, 2.0 * M * N * K, rows=M,
-                nbytes16=2.0 * M * (N + K) + 4.0 * N * K)
+    nb, fl, nb16 = _wgrad_work(M, N, K, dy16, x16)
+    ev = _probe('linear_wgrad', nb, fl, rows=M, nbytes16=nb16)
     check(_l().leod_linear_wgrad(_p(dy), N, _p(x), K1, _p(stats), _p(ln_w), _p(ln_b), _p(x2),
                                   (x2.shape[-1] if x2 is not None else 0), K1, _p(dW), _p(dbias), M, N, K,
-                                  (1 if dy16 else 0) | (4 if xh else (2 if x16 else 0)), _stream()), 'linear_wgrad')
+                                  1 if dy16 else 0, _x_fmt(x, stats, gelu), _stream()), 'linear_wgrad')
     if ev is not None:
         ev.record()
-
-
-def _x_fmt(x, stats, gelu):
-    if gelu:
-        return 2
-    if x.dtype is torch.bfloat16:
-        return 3
-    if x.dtype is torch.float16:
-        return 4
-    return 1 if stats is not None else 0
 
 
 def linear_wgrad_group(problems) -> bool:
@@ -530,9 +530,8 @@ def linear_wgrad_group(problems) -> bool:
         for t_ in (dW, p.get('dbias'), p.get('stats'), p.get('ln_w'), p.get('ln_b')):
             _ck(t_, name='linear_wgrad_group')
         Ns.append(N); Ks.append(K); dyf.append(1 if dy16 else 0); xf.append(fmt)
-        nb += (2.0 if dy16 else 4.0) * M * N + (2.0 if fmt >= 2 else 4.0) * M * K + 4.0 * N * K
-        fl += 2.0 * M * N * K
-        nb16 += 2.0 * M * (N + K) + 4.0 * N * K
+        w = _wgrad_work(M, N, K, dy16, fmt >= 2)
+        nb += w[0]; fl += w[1]; nb16 += w[2]
     if M >= 8192 and _stream() not in _WORKSPACES:
         _wgrad_workspace(problems[0]['dW'].device)
     ev = _probe('linear_wgrad', nb, fl, rows=M, nbytes16=nb16)

@@ -4,7 +4,7 @@ separate runs, MI355X_MICROARCH.md).  Corrections applied as that guide prescrib
 coalesced reads reports half the bytes -> x2.
 
 The family is delimited by marker dispatches (LEOD_FAMILY_MARKERS=1: the library launches ``leod_family_marker_kernel`` in front of and
-behind every ``leod_linear_wgrad`` / ``leod_linear_wgrad_gelu16`` call; single-stream eager run, so dispatch order = program order): the
+behind every ``leod_linear_wgrad`` / ``leod_linear_wgrad_group`` call; single-stream eager run, so dispatch order = program order): the
 bytes of every dispatch between a begin and an end marker are summed and divided by the number of marker pairs -- the same launches the
 HIP-event probe of bench.py brackets (36 per training step), whatever kernels they resolve to (round 3 divided the bytes of the name
 pattern wgrad_wide|wgradw by 102 launches of which 30 were 1x1-conv weight gradients: 208 MB reported, 284 MB true).
@@ -49,7 +49,7 @@ def main(fdb, wdb, out_json, out_csv):
             wr.writerow([name, len(f.get(name, [])), f'{sum(f.get(name, [])):.1f}', f'{sum(w.get(name, [])):.1f}'])
     rd = 2 * 1024 * tot_f / max(nf, 1)
     wt = 1024 * tot_w / max(nw, 1)
-    json.dump({'kernel': 'every dispatch inside leod_linear_wgrad / leod_linear_wgrad_gelu16 (family markers)', 'launches_sampled': [nf, nw],
+    json.dump({'kernel': 'every dispatch inside leod_linear_wgrad / leod_linear_wgrad_group (family markers)', 'launches_sampled': [nf, nw],
                'hbm_bytes_per_launch': round(rd + wt), 'read_bytes_per_launch': round(rd), 'write_bytes_per_launch': round(wt),
                'source': os.path.relpath(out_csv)}, open(out_json, 'w'), indent=1)
     print(open(out_json).read())
