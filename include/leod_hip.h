@@ -410,6 +410,14 @@ int leod_mixed_density_i8(const long* x, const long* y, const long* pol, const l
  * order and the 2*bins channel planes of each frame reversed. */
 int leod_augment_u8(const unsigned char* src, unsigned char* dst, const int* params, int T, int B, int C, int H, int W,
                     leod_stream_t stream);
+/* The same pass with a rotation between the flip and the zoom (data/utils/augmentor.py:359-386,464-476: hflip -> rotate ->
+ * zoom; torchvision rotate with NEAREST, expand=False, fill=None).  rot[b] = {cos a, sin a} of the sample's counter-clockwise
+ * angle as fp32 (2 floats per sample); {1, 0} = no rotation for that sample.  Source index in fp32, one rounding per operation:
+ * cx = 0.5*W - 0.5, cy = 0.5*H - 0.5, sx = rint(c*(x-cx) - s*(y-cy) + cx), sy = rint(s*(x-cx) + c*(y-cy) + cy) (round half to
+ * even, as grid_sample(nearest) over affine_grid(align_corners=False)); pixels whose source falls outside the frame are 0.
+ * Same refusals as leod_augment_u8, plus a NULL rot. */
+int leod_augment_rot_u8(const unsigned char* src, unsigned char* dst, const int* params, const float* rot, int T, int B, int C,
+                        int H, int W, leod_stream_t stream);
 
 /* dgrad of a Linear fused with the LayerNorm backward of its producer (x -> norm -> Linear, maxvit.py:267-269,110-118):
  * dx[M,K] = LN-backward(dy[M,N] @ W[N,K]) (+ dres), dgamma[K] += sum dn*xhat, dbeta[K] += sum dn, with x[M,K] the LayerNorm

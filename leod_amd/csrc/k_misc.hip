@@ -509,3 +509,87 @@ LEOD_API int leod_augment_u8(const unsigned char* src, unsigned char* dst, const
     hipLaunchKernelGGL(augment_u8_kernel, grid, dim3(256), 0, stream, src, dst, params, T, B, C, H, W);
     return leod_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same gather with a rotation between the flip and the zoom (data/utils/augmentor.py:359-386,464-476: hflip -> rotate
+// -> zoom-in | zoom-out; the frames go through torchvision's rotate(interpolation=NEAREST, expand=False, fill=None)).
+// rot[b] = {cos a, sin a} of the sample's angle (counter-clockwise, computed in double on the host and rounded to fp32);
+// {1, 0} = no rotation for that sample, which then takes exactly the path of augment_u8_kernel.
+// Backwards from an output pixel: invert the zoom as above -> integer pixel (y1, x1) of the rotated frame; invert the rotation
+// -> (sy, sx) of the flipped frame; un-flip; tflip plane selection.  Whatever falls outside the frame is 0 (the corners of every
+// rotated frame), and no load is issued for it.
+// Index rule = affine_grid(align_corners=False) + grid_sample(nearest), i.e. rotation about the pixel-centre midpoint
+// (W/2 - 0.5, H/2 - 0.5) and round-half-to-even, in fp32 with one rounding per operation (no contraction into FMAs):
+//   sxf = c*(x1-cx) - s*(y1-cy) + cx;  syf = s*(x1-cx) + c*(y1-cy) + cy;  sx = rint(sxf);  sy = rint(syf).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool rotate_source(int y1, int x1, float c, float s, float cx, float cy, int H, int W, int& sy, int& sx) {
+#pragma clang fp contract(off)
+    const float dx = (float)x1 - cx, dy = (float)y1 - cy;
+    const float sxf = c * dx - s * dy + cx;
+    const float syf = s * dx + c * dy + cy;
+    sx = (int)rintf(sxf);
+    sy = (int)rintf(syf);
+    return (unsigned)sx < (unsigned)W && (unsigned)sy < (unsigned)H;
+}
+
+__global__ __launch_bounds__(256) void augment_rot_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                             const int* __restrict__ params, const float* __restrict__ rot,
+                                                             int T, int B, int C, int H, int W) {
+    // grid: x = pixel quads of one plane, y = (t*B + b)*C + c
+    const int plane = blockIdx.y;
+    const int b = (plane / C) % B;
+    const int* pp = params + 7 * b;
+    const int hflip = pp[0], mode = pp[1], x0 = pp[2], y0 = pp[3], wh = pp[4], ww = pp[5];
+    const float rc = rot[2 * b], rs = rot[2 * b + 1];
+    const bool rotated = !(rc == 1.0f && rs == 0.0f);
+    const float cx = 0.5f * (float)W - 0.5f, cy = 0.5f * (float)H - 0.5f;
+    int src_plane = plane;
+    if (pp[6]) {
+        const int c = plane % C, t = plane / (C * B);
+        src_plane = ((T - 1 - t) * B + b) * C + (C - 1 - c);
+    }
+    const uint8_t* sp = src + (long)src_plane * H * W;
+    uint8_t* dp = dst + (long)plane * H * W;
+    const int quads = H * (W / 4);
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < quads; e += gridDim.x * 256) {
+        const int y = e / (W / 4), xq = (e - y * (W / 4)) * 4;
+        uint32_t packed = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = xq + k;
+            int sy = y, sx = x;
+            bool live = true;
+            if (mode == 1) {                                  // zoom-in: window (wh x ww) at (y0, x0) -> full frame
+                sy = y0 + nearest_exact(y, wh, H);
+                sx = x0 + nearest_exact(x, ww, W);
+            } else if (mode == 2) {                           // zoom-out: full frame -> window at (y0, x0), zeros elsewhere
+                const int j = y - y0, i = x - x0;
+                live = (unsigned)j < (unsigned)wh && (unsigned)i < (unsigned)ww;
+                sy = live ? nearest_exact(j, H, wh) : 0;
+                sx = live ? nearest_exact(i, W, ww) : 0;
+            }
+            if (rotated) {                                    // the zooms act on the rotated frame
+                int ry, rx;
+                live = rotate_source(sy, sx, rc, rs, cx, cy, H, W, ry, rx) && live;
+                sy = live ? ry : 0;
+                sx = live ? rx : 0;
+            }
+            if (hflip) sx = W - 1 - sx;                       // ... and the rotation on the already flipped frame
+            live = live && (unsigned)sx < (unsigned)W && (unsigned)sy < (unsigned)H;      // a bad window never becomes a bad address
+            const uint32_t v = live ? sp[live ? (long)sy * W + sx : 0] : 0u;
+            packed |= v << (8 * k);
+        }
+        *reinterpret_cast<uint32_t*>(dp + (long)y * W + xq) = packed;
+    }
+}
+
+LEOD_API int leod_augment_rot_u8(const unsigned char* src, unsigned char* dst, const int* params, const float* rot, int T, int B, int C,
+                                 int H, int W, hipStream_t stream) {
+    if (!src || !dst || !params || !rot || src == dst || (W & 3) || T <= 0 || B <= 0 || C <= 0 || H <= 0 || W <= 0) return LEOD_ERR_ARG;
+    const long planes = (long)T * B * C;
+    if (planes > 65535) return LEOD_ERR_UNSUPPORTED;            // grid.y limit, as leod_augment_u8
+    const int quads = H * (W / 4);
+    dim3 grid(min(cdiv(quads, 256), 64), (unsigned)planes);
+    hipLaunchKernelGGL(augment_rot_u8_kernel, grid, dim3(256), 0, stream, src, dst, params, rot, T, B, C, H, W);
+    return leod_launch_status();
+}

@@ -7,6 +7,7 @@ carry t == 0; the loss target layout is [B, Nmax, 7] = (cls, cx, cy, w, h, obj, 
 (labels.py:543-603).  BBOX_DTYPE is the 40-byte on-disk record (labels.py:12-16)."""
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -145,6 +146,32 @@ class ObjectLabels:
         self._set('y', o[:, 2] * scaling_multiplier)
         self._set('w', x1 - self.object_labels[:, 1])
         self._set('h', y1 - self.object_labels[:, 2])
+        self.remove_flat_labels_()
+
+    def rotate_(self, angle_deg: float) -> None:
+        """Counter-clockwise rotation by ``angle_deg`` (labels.py:327-370): the four corners of every box turn about the INTEGER centre
+        (W // 2, H // 2) -- not the pixel-centre midpoint the frame warp turns about; mirrored as is -- with an fp32 matrix; the box
+        becomes the axis-aligned hull of the corners clamped to the frame, boxes left without area are dropped."""
+        if len(self) == 0:
+            return
+        o = self.object_labels
+        x, y, w, h = o[:, 1], o[:, 2], o[:, 3], o[:, 4]
+        points = th.stack((th.stack((x, y), dim=1), th.stack((x + w, y), dim=1),
+                           th.stack((x, y + h), dim=1), th.stack((x + w, y + h), dim=1)), dim=0)      # [4, N, 2]
+        height, width = self.input_size_hw
+        center = th.tensor([width // 2, height // 2], device=o.device)
+        angle_rad = angle_deg / 180 * math.pi
+        rot_matrix = th.tensor([[math.cos(angle_rad), math.sin(angle_rad)],
+                                [-math.sin(angle_rad), math.cos(angle_rad)]], device=o.device)
+        points = th.einsum('ij,pnj->pni', rot_matrix, points - center) + center
+        x0 = th.clamp(th.min(points[..., 0], dim=0)[0], min=0, max=width - 1)
+        y0 = th.clamp(th.min(points[..., 1], dim=0)[0], min=0, max=height - 1)
+        x1 = th.clamp(th.max(points[..., 0], dim=0)[0], min=0, max=width - 1)
+        y1 = th.clamp(th.max(points[..., 1], dim=0)[0], min=0, max=height - 1)
+        self._set('x', x0)
+        self._set('y', y0)
+        self._set('w', x1 - x0)
+        self._set('h', y1 - y0)
         self.remove_flat_labels_()
 
     def zoom_in_and_rescale_(self, zoom_coordinates_x0y0, zoom_in_factor: float) -> None:
@@ -394,6 +421,12 @@ class SparselyBatchedObjectLabels:
         for i, l in enumerate(self.sparse_object_labels_batch):
             if l is not None and len(l) == 0:
                 self.sparse_object_labels_batch[i] = None
+
+    def rotate_(self, *args, **kwargs):
+        """labels.py:685-688: frames whose boxes all left the frame stay as empty labels (unlike the zooms, no None)."""
+        for l in self.sparse_object_labels_batch:
+            if l is not None:
+                l.rotate_(*args, **kwargs)
 
     def zoom_in_and_rescale_(self, *args, **kwargs):
         for l in self.sparse_object_labels_batch:

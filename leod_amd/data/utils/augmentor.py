@@ -2,15 +2,18 @@
 
 What is random stays on the host and draws from torch's RNG in the reference's order, so a seed gives the same
 ``AugmentationState`` as the reference's ``RandomSpatialAugmentorGenX`` (tests/golden/g14_augment.npz).  What touches
-pixels -- flip, zoom-in (crop + nearest-exact resize), zoom-out (nearest-exact resize + paste) -- is ONE gather kernel over
-the uint8 representation of a whole batch of sequences (``leod_augment_u8``): the reference runs ``flip`` /
-``interpolate`` / slice assignment per sample and timestep in the dataloader workers.  Labels are transformed by the
-``ObjectLabels`` methods mirrored from data/genx_utils/labels.py.
+pixels -- flip, rotation (nearest), zoom-in (crop + nearest-exact resize), zoom-out (nearest-exact resize + paste) -- is ONE
+gather kernel over the uint8 representation of a whole batch of sequences (``leod_augment_u8``; ``leod_augment_rot_u8`` when
+a sample of the batch drew a rotation): the reference runs ``flip`` / ``rotate`` / ``interpolate`` / slice assignment per
+sample and timestep in the dataloader workers.  Labels are transformed by the ``ObjectLabels`` methods mirrored from
+data/genx_utils/labels.py.
 
-Rotation (probability 0 in every shipped config) and the flow / image data types are not part of the LEOD path.
+The flow / image data types are not part of the LEOD path.
 """
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+
+import math
 
 import torch
 import torch as th
@@ -166,7 +169,7 @@ class RandomSpatialAugmentorGenX:
     def __call__(self, data_dict: Dict[Any, Any]) -> Dict[Any, Any]:
         """One loader sample (reference ``__call__``, augmentor.py:455-476): the labels (visible and withheld) are transformed
         here on the host; the event frames are NOT touched -- the drawn state rides along under ``DataType.AUGM_STATE`` and
-        the whole batch is flipped / zoomed by one ``leod_augment_u8`` launch on the device (``augment_events``)."""
+        the whole batch is flipped / rotated / zoomed by one gather launch on the device (``augment_events``)."""
         from leod_amd.data.utils.types import DataType
         primary = data_dict[DataType.OBJLABELS_SEQ]
         others = [data_dict[k] for k in (DataType.SKIPPED_OBJLABELS_SEQ,) if k in data_dict]
@@ -183,8 +186,8 @@ class RandomSpatialAugmentorGenX:
     def augment_sample_labels(self, labels: Sequence[Optional[ObjectLabels]],
                               extra: Sequence[Sequence[Optional[ObjectLabels]]] = ()) -> AugmentationState:
         """Everything ``__call__`` of the reference does for ONE loader sample except the pixel work (augmentor.py:455-476,
-        in that order): draw the state, flip the labels, sample the zoom-in window from the (flipped) labels, transform
-        the labels (``extra``: further label lists of the sample that follow the same transform, e.g. the withheld labels).
+        in that order): draw the state, flip and rotate the labels, sample the zoom-in window from the (flipped, rotated) labels,
+        transform the labels (``extra``: further label lists of the sample that follow the same transform, e.g. the withheld labels).
         Returns a copy of the resulting state; feed the states of a batch to ``augment_events``."""
         import copy
         every = [labels] + [list_ for list_ in extra]
@@ -192,12 +195,14 @@ class RandomSpatialAugmentorGenX:
             self.randomize_augmentation()
         st = self.augm_state
         assert not st.apply_t_flip, 'should do this outside this class (due to streaming loading mode)'
-        if st.rotation.active:
-            raise NotImplementedError('rotation augmentation (probability 0 in every shipped config)')
         if st.apply_h_flip:
             for lab in (l for list_ in every for l in list_):
                 if lab is not None:
                     lab.flip_lr_()
+        if st.rotation.active:                       # boxes that leave the frame are dropped, emptied frames stay (labels.py:685-688)
+            for lab in (l for list_ in every for l in list_):
+                if lab is not None:
+                    lab.rotate_(st.rotation.angle_deg)
         if st.zoom_in.active:
             self.sample_zoom_in(labels)
             if st.zoom_in.active:
@@ -219,10 +224,18 @@ def state_to_params(state: AugmentationState, hw: Tuple[int, int]) -> List[int]:
     """{hflip, mode, x0, y0, win_h, win_w, tflip} of ``leod_augment_u8``; window sizes as the reference computes them
     (``int(size / factor)``, cropped at the frame border like the slice ``[y0:y0+h, x0:x0+w]``).  ``apply_t_flip`` is
     the loader's ``time_flip_data`` (sequence_base.py:207-227: frames reversed, channel planes reversed) -- the reference's
-    augmentor leaves it to the dataset (augmentor.py:464-465), here it rides in the same gather pass."""
-    if state.rotation.active:
-        raise NotImplementedError('rotation augmentation (probability 0 in every shipped config)')
+    augmentor leaves it to the dataset (augmentor.py:464-465), here it rides in the same gather pass.  The rotation of the
+    state travels separately (``state_to_rot``)."""
     return _spatial_params(state, hw) + [int(bool(state.apply_t_flip))]
+
+
+def state_to_rot(state: AugmentationState) -> List[float]:
+    """{cos a, sin a} of ``leod_augment_rot_u8`` for the state's counter-clockwise angle, from Python floats like the matrix
+    torchvision's ``rotate`` builds (the binding rounds them to fp32); {1, 0} = no rotation."""
+    if not state.rotation.active or state.rotation.angle_deg == 0:
+        return [1.0, 0.0]
+    a = math.radians(state.rotation.angle_deg)
+    return [math.cos(a), math.sin(a)]
 
 
 def _spatial_params(state: AugmentationState, hw: Tuple[int, int]) -> List[int]:
@@ -244,12 +257,19 @@ def _spatial_params(state: AugmentationState, hw: Tuple[int, int]) -> List[int]:
 
 
 def augment_events(ev_seq: th.Tensor, states: Sequence[AugmentationState]) -> th.Tensor:
-    """ev_seq [T,B,C,H,W] uint8 on the device, one state per batch sample -> augmented copy (one kernel launch)."""
+    """ev_seq [T,B,C,H,W] uint8 on the device, one state per batch sample -> augmented copy (one kernel launch: the rotating
+    gather only when a sample of the batch rotates, otherwise ``leod_augment_u8`` as ever)."""
     assert ev_seq.dim() == 5 and ev_seq.dtype == th.uint8 and ev_seq.is_cuda and ev_seq.is_contiguous()
     T, B, C, H, W = ev_seq.shape
     assert len(states) == B
     params = th.tensor([state_to_params(s, (H, W)) for s in states], dtype=th.int32).to(ev_seq.device, non_blocking=True)
     out = th.empty_like(ev_seq)
+    rots = [state_to_rot(s) for s in states]
+    if any(r != [1.0, 0.0] for r in rots):
+        rot = th.tensor(rots, dtype=th.float64).to(th.float32).to(ev_seq.device, non_blocking=True)
+        check(lib().leod_augment_rot_u8(ev_seq.data_ptr(), out.data_ptr(), params.data_ptr(), rot.data_ptr(), T, B, C, H, W,
+                                        th.cuda.current_stream().cuda_stream), 'augment_rot_u8')
+        return out
     check(lib().leod_augment_u8(ev_seq.data_ptr(), out.data_ptr(), params.data_ptr(), T, B, C, H, W,
                                 th.cuda.current_stream().cuda_stream), 'augment_u8')
     return out
@@ -257,12 +277,14 @@ def augment_events(ev_seq: th.Tensor, states: Sequence[AugmentationState]) -> th
 
 def augment_labels(labels: Sequence[Optional[ObjectLabels]], state: AugmentationState) -> List[Optional[ObjectLabels]]:
     """The label side of ``RandomSpatialAugmentorGenX.__call__`` for the frames of ONE sample (in place, like the
-    reference): flip, then zoom-in or zoom-out (augmentor.py:455-476)."""
+    reference): flip, rotation, then zoom-in or zoom-out (augmentor.py:455-476)."""
     for lab in labels:
         if lab is None:
             continue
         if state.apply_h_flip:
             lab.flip_lr_()
+        if state.rotation.active:
+            lab.rotate_(state.rotation.angle_deg)
         if state.zoom_in.active:
             lab.zoom_in_and_rescale_((state.zoom_in.x0, state.zoom_in.y0), state.zoom_in.zoom_in_factor)
         if state.zoom_out.active:

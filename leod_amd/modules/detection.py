@@ -120,9 +120,9 @@ class Module(_Base):
             if tidx not in self.label_subsample_idx:
                 seq[tidx].set_non_gt_labels_to_none_()
         states = data.get(DataType.AUGM_STATE, None)
-        if states is not None and any(s.apply_h_flip or s.zoom_in.active or s.zoom_out.active for s in states):
+        if states is not None and any(s.apply_h_flip or s.rotation.active or s.zoom_in.active or s.zoom_out.active for s in states):
             # spatial augmentation of the whole batch in ONE gather launch (the loaders transformed the labels on the host
-            # and left the frames untouched; the reference flips / zooms every frame in the dataloader workers)
+            # and left the frames untouched; the reference flips / rotates / zooms every frame in the dataloader workers)
             from leod_amd.data.utils.augmentor import augment_events
             f0 = data[DataType.EV_REPR][0]
             if not (th.is_tensor(f0) and f0.is_cuda):
