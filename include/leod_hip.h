@@ -173,6 +173,18 @@ int leod_set_workspace(void* ws, long bytes, leod_stream_t stream);
 int leod_linear_wgrad(const float* dy, long lddy, const float* x, long ldx, const float* stats, const float* ln_w,
                       const float* ln_b, const float* x2, long ldx2, int K1, float* dW, float* dbias, int M, int N,
                       int K, int dy_fmt, int x_fmt, leod_stream_t stream);
+/* Which kernel leod_linear_wgrad runs for this problem in the current precision mode -- a query: nothing is launched, no memory is read.
+ * has_stats: stats, ln_w and ln_b are given; has_x2: x2 is given.  The call itself switches on the same value, so the two cannot differ.
+ *   100 + T            LDS-DMA kernel, T x T blocks of 16 columns per workgroup (T = 4, 6, 8)
+ *   200 + c            register-staged wide kernel, instantiation c = 1 .. 16
+ *   300 + c            wgradw kernel, configuration c = 1 .. 5 (48 x 48, 192 x 48, 48 x 192, 96 x 96 with 32-row chunks, 96 x 96 with 16-row chunks)
+ *   400 + 10 TN + TK   wgrad16 kernel on TN x TK blocks of 16 columns (33, 22, 44, 14, 41, 11)
+ *   0                  M <= 0: nothing to do;    -1 / -3: what leod_linear_wgrad returns for these arguments (NULL pointers apart)
+ * One thing is not known before the launch: a 100 + T problem on a stream that has no registered workspace while none can be allocated
+ * (the stream is being captured) runs on the route it would have without the LDS-DMA kernel.  Register a workspace first
+ * (leod_set_workspace) and the answer is what runs. */
+int leod_linear_wgrad_route(int M, int N, int K, long lddy, long ldx, long ldx2, int K1, int dy_fmt, int x_fmt, int has_stats,
+                            int has_x2);
 
 /* LayerNorm over channels (eps 1e-5), maxvit.py:172-178 and its autograd. */
 int leod_layernorm_fwd(const float* x, const float* w, const float* b, float* y, float* stats, int M, int C, float eps,

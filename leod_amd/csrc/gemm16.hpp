@@ -1584,7 +1584,7 @@ template <int TN, int TK, class XL>
 static inline int launch_wgrad16(const float* dy, long lddy, const XL& xl, float* dW, long ldw, float* dbias,
                                  int M, int N, int K, hipStream_t s, int dyfmt = 0) {
     if (M <= 0) return LEOD_OK;
-    if ((N & 3) || (K & 3) || (lddy & 3)) return LEOD_ERR_ARG;      // 16-byte row loads
+    if ((N & 3) || (K & 3) || (lddy & 3)) return LEOD_ERR_ARG;      // 16-byte row loads (wgrad_rows16b_ok, below)
     const int tiles = cdiv(N, TN * 16) * cdiv(K, TK * 16);
     // ~768 workgroups in total, at least 4 staged chunks (128 rows) each: every workgroup ends with one fp32 atomic
     // per dW element, so a few fat workgroups beat many thin ones
@@ -1960,23 +1960,41 @@ static inline int launch_wgradw_cfg(const float* dy, long lddy, const XL& xl, fl
     return leod_launch_status();
 }
 
-// shape-driven choice of the workgroup tile (see the kernel header)
+// shape-driven choice of the workgroup tile (see the kernel header): the configurations of wgradw_kernel, numbered 1..5 in the order of
+// launch_wgradw_as (the Linear router reports them as 300 + cfg)
 template <class XL>
-static inline int launch_wgradw(const float* dy, long lddy, const XL& xl, float* dW, long ldw, float* dbias,
-                                int M, int N, int K, hipStream_t s, int dyfmt = 0) {
-    if (M <= 0) return LEOD_OK;
-    if ((N & 3) || (K & 3) || (lddy & 3)) return LEOD_ERR_ARG;      // 16-byte row loads
-    if (K <= 48 && N <= 48) return launch_wgradw_cfg<3, 3, 3, 3, 64>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+static inline int wgradw_cfg(const XL& xl, int M, int N, int K) {
+    if (K <= 48 && N <= 48) return 1;
     // 32-row chunks (half the barriers, twice the bytes in flight per round) pay for the short row ranges of stages 3-4 with plain or
     // fp16 X rows: 72 -> 63 us (fc2, stage 4), 118 -> 94 us (LSTM); the LayerNorm variant spills at 128 VGPRs and the long ranges of
     // stage 2 are indifferent or slower
     static const int rc32_on = 1;
     bool rc32 = false;
     if constexpr (x_two_phase<XL>::value) rc32 = rc32_on && M <= 65536 && xl.x_mode() != XM_LN && leod_precision() == 1;
-    if (K <= 48) return launch_wgradw_cfg<12, 3, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
-    if (N <= 48) return launch_wgradw_cfg<3, 12, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
-    if (rc32) return launch_wgradw_cfg<6, 6, 3, 3, 32>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
-    return launch_wgradw_cfg<6, 6, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+    if (K <= 48) return 2;
+    if (N <= 48) return 3;
+    return rc32 ? 4 : 5;
+}
+// 16-byte row loads of wgradw_kernel / wgrad16_kernel
+static inline bool wgrad_rows16b_ok(long lddy, int N, int K) { return !((N & 3) || (K & 3) || (lddy & 3)); }
+template <class XL>
+static inline int launch_wgradw_as(int cfg, const float* dy, long lddy, const XL& xl, float* dW, long ldw, float* dbias,
+                                   int M, int N, int K, hipStream_t s, int dyfmt = 0) {
+    if (M <= 0) return LEOD_OK;
+    if (!wgrad_rows16b_ok(lddy, N, K)) return LEOD_ERR_ARG;
+    switch (cfg) {
+        case 1: return launch_wgradw_cfg<3, 3, 3, 3, 64>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+        case 2: return launch_wgradw_cfg<12, 3, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+        case 3: return launch_wgradw_cfg<3, 12, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+        case 4: return launch_wgradw_cfg<6, 6, 3, 3, 32>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+        case 5: return launch_wgradw_cfg<6, 6, 3, 3, 16>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+    }
+    return LEOD_ERR_ARG;
+}
+template <class XL>
+static inline int launch_wgradw(const float* dy, long lddy, const XL& xl, float* dW, long ldw, float* dbias,
+                                int M, int N, int K, hipStream_t s, int dyfmt = 0) {
+    return launch_wgradw_as(wgradw_cfg(xl, M, N, K), dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
 }
 // large row counts only: small problems keep the round-robin kernel (more workgroups per output tile)
 static inline bool use_wgradw(int M) {

@@ -27,30 +27,68 @@ struct FamilyMarker {
     ~FamilyMarker() { if (on) hipLaunchKernelGGL(leod_family_marker_kernel, dim3(1), dim3(1), 0, s, 0); }
 };
 
-// The one routing function of the Linear weight gradients: the fully described problem -> the kernel that runs it.  LDS-DMA kernel
-// (wgrad_dma.hpp), then the register-staged wide kernel (wgrad_bf16.hpp), then wgradw_kernel, then the tile ladder of wgrad16_kernel.
-static int route_linear_wgrad(const float* dy, long lddy, int dyfmt, const XRows& xl, float* dW, float* dbias, int M, int N, int K,
-                              hipStream_t stream) {
+// The one routing function of the Linear weight gradients: the fully described problem -> the kernel that runs it, as a route code.
+// LDS-DMA kernel (wgrad_dma.hpp), then the register-staged wide kernel (wgrad_bf16.hpp), then wgradw_kernel, then the tile ladder of
+// wgrad16_kernel.  It launches nothing and reads no device memory (of xl only the mode, the strides, K1 and WHETHER stats / x2 are set):
+//   100 + T           LDS-DMA kernel on T x T blocks of 16 columns (T = 4, 6, 8)
+//   200 + combo       wide kernel, combo 1..16 of wgrad_wide_combo
+//   300 + cfg         wgradw_kernel, cfg 1..5 of wgradw_cfg
+//   400 + 10 TN + TK  wgrad16_kernel<TN, TK>
+//   0                 M <= 0: nothing to launch (LEOD_OK);   < 0: LEOD_ERR_*
+// dma = false: the LDS-DMA kernel is not available (launch_linear_wgrad: its workspace could not be had) -- where the problem goes then.
+enum : int { WGR_NONE = 0, WGR_DMA = 100, WGR_WIDE = 200, WGR_WGRADW = 300, WGR_LADDER = 400 };
+static int wgrad_route(const XRows& xl, long lddy, int dyfmt, int M, int N, int K, bool dma = true) {
     const int xm = xl.x_mode();
-    if (xm == XM_BF16 || xm == XM_F16) {            // 16-bit rows (the attention output; fp16 in precision mode 16f): the bf16-MFMA kernels only
-        if (xl.stats || xl.x2) return LEOD_ERR_ARG;
-        if (!use_wgrad_wide(xl, lddy, M, N, K, dyfmt) && !wgrad_dma_ok(xl, lddy, M, N, K, dyfmt)) return LEOD_ERR_UNSUPPORTED;
+    const bool x16 = xm == XM_BF16 || xm == XM_F16; // 16-bit rows (the attention output; fp16 in precision mode 16f): the bf16-MFMA kernels only
+    if (x16 && (xl.stats || xl.x2)) return LEOD_ERR_ARG;
+    if (dma && wgrad_dma_ok(xl, lddy, M, N, K, dyfmt)) return WGR_DMA + wgd_tile(N, K);
+    if (use_wgrad_wide(xl, lddy, M, N, K, dyfmt)) return WGR_WIDE + wgrad_wide_combo(xl, N, K, dyfmt);
+    if (x16) return LEOD_ERR_UNSUPPORTED;
+    if (M <= 0) return WGR_NONE;
+    if (!wgrad_rows16b_ok(lddy, N, K)) return LEOD_ERR_ARG;
+    const bool f32 = leod_precision() != 1;         // 16-bit tensors exist in the 16-bit precision modes only
+    if (use_wgradw(M)) return (f32 && (dyfmt || xm == XM_GELU16)) ? LEOD_ERR_ARG : WGR_WGRADW + wgradw_cfg(xl, M, N, K);
+    if (f32 && dyfmt) return LEOD_ERR_ARG;
+    if (N % 48 == 0 && K % 48 == 0) return WGR_LADDER + 33;
+    // the fp16 pre-activation had an entry point of its own, whose ladder ended here; it is reachable (any M < 8192 with widths that
+    // are not multiples of 48), so that mode keeps its tile
+    if (xm == XM_GELU16) return WGR_LADDER + 44;
+    if (N % 32 == 0 && K % 32 == 0 && (N % 64 || K % 64)) return WGR_LADDER + 22;
+    if (N >= 64 && K >= 64) return WGR_LADDER + 44;
+    if (K >= 64) return WGR_LADDER + 14;
+    if (N >= 64) return WGR_LADDER + 41;
+    return WGR_LADDER + 11;
+}
+// ... and the switch that launches what wgrad_route decided
+static int launch_linear_wgrad(int route, const float* dy, long lddy, int dyfmt, const XRows& xl, float* dW, float* dbias, int M, int N, int K,
+                               hipStream_t stream) {
+    if (route <= 0) return route;                   // WGR_NONE == LEOD_OK
+    const long ldw = (long)K;
+    if (route < WGR_WIDE) {
+        // the one condition wgrad_route cannot know: no workspace is registered for the stream and none can be allocated (the stream is
+        // being captured, or hipMalloc failed) -- nothing was launched, and the problem takes the route it has without this kernel
+        const int rc = launch_wgrad_dma(route - WGR_DMA, dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+        return rc != LEOD_ERR_UNSUPPORTED ? rc : launch_linear_wgrad(wgrad_route(xl, lddy, dyfmt, M, N, K, false), dy, lddy, dyfmt, xl, dW, dbias, M, N, K, stream);
     }
-    if (wgrad_dma_ok(xl, lddy, M, N, K, dyfmt)) {
-        const int rc = launch_wgrad_dma(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-        if (rc != LEOD_ERR_UNSUPPORTED) return rc;
+    if (route < WGR_WGRADW) return launch_wgrad_wide(route - WGR_WIDE, dy, lddy, xl, dW, ldw, dbias, M, N, K, stream);
+    if (route < WGR_LADDER) return launch_wgradw_as(route - WGR_WGRADW, dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+    switch (route - WGR_LADDER) {
+        case 33: return launch_wgrad16<3, 3>(dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+        case 22: return launch_wgrad16<2, 2>(dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+        case 44: return launch_wgrad16<4, 4>(dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+        case 14: return launch_wgrad16<1, 4>(dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+        case 41: return launch_wgrad16<4, 1>(dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
+        case 11: return launch_wgrad16<1, 1>(dy, lddy, xl, dW, ldw, dbias, M, N, K, stream, dyfmt);
     }
-    if (use_wgrad_wide(xl, lddy, M, N, K, dyfmt)) return launch_wgrad_wide(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    if (use_wgradw(M)) return launch_wgradw(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    if (N % 48 == 0 && K % 48 == 0) return launch_wgrad16<3, 3>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    // the fp16 pre-activation had an entry point of its own, whose ladder ended here; it is reachable (any M < 8192, or precision mode
-    // f32, with widths that are not multiples of 48), so that mode keeps its tile
-    if (xm == XM_GELU16) return launch_wgrad16<4, 4>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    if (N % 32 == 0 && K % 32 == 0 && (N % 64 || K % 64)) return launch_wgrad16<2, 2>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    if (N >= 64 && K >= 64) return launch_wgrad16<4, 4>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    if (K >= 64) return launch_wgrad16<1, 4>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    if (N >= 64) return launch_wgrad16<4, 1>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
-    return launch_wgrad16<1, 1>(dy, lddy, xl, dW, (long)K, dbias, M, N, K, stream, dyfmt);
+    return LEOD_ERR_ARG;
+}
+
+// what leod_linear_wgrad takes at all: the (dy_fmt, x_fmt) vocabulary and which of stats / ln_w + ln_b / x2 go with which x_fmt
+static bool wgrad_formats_ok(int dy_fmt, int x_fmt, bool has_stats, bool has_ln_wb, bool has_x2) {
+    if ((dy_fmt != 0 && dy_fmt != 1) || !xm_valid(x_fmt)) return false;
+    if ((x_fmt == XM_LN) != has_stats || (x_fmt == XM_LN && !has_ln_wb)) return false;
+    if (x_fmt == XM_GELU16 && (has_x2 || dy_fmt)) return false;             // fp32 dy, no concat: all that the former entry of this mode took
+    return true;
 }
 
 // dW[N,K] += dy[M,N]^T @ X[M,K] ; dbias[N] += colsum(dy).  dy_fmt: 0 fp32 rows, 1 bf16 rows.  x_fmt (XMode): what x holds and how X comes
@@ -59,13 +97,25 @@ static int route_linear_wgrad(const float* dy, long lddy, int dyfmt, const XRows
 LEOD_API int leod_linear_wgrad(const float* dy, long lddy, const float* x, long ldx, const float* stats,
                                const float* ln_w, const float* ln_b, const float* x2, long ldx2, int K1,
                                float* dW, float* dbias, int M, int N, int K, int dy_fmt, int x_fmt, hipStream_t stream) {
-    if (!dy || !x || !dW || (dy_fmt != 0 && dy_fmt != 1) || !xm_valid(x_fmt)) return LEOD_ERR_ARG;
-    if ((x_fmt == XM_LN) != (stats != nullptr) || (x_fmt == XM_LN && (!ln_w || !ln_b))) return LEOD_ERR_ARG;
-    if (x_fmt == XM_GELU16 && (x2 || dy_fmt)) return LEOD_ERR_ARG;          // fp32 dy, no concat: all that the former entry of this mode took
+    if (!dy || !x || !dW || !wgrad_formats_ok(dy_fmt, x_fmt, stats != nullptr, ln_w && ln_b, x2 != nullptr)) return LEOD_ERR_ARG;
     FamilyMarker fm(stream);
     XRows xl{x, ldx, stats, ln_w, ln_b, x2, ldx2, K1};
     xl.set_mode(x_fmt);
-    return route_linear_wgrad(dy, lddy, dy_fmt, xl, dW, dbias, M, N, K, stream);
+    return launch_linear_wgrad(wgrad_route(xl, lddy, dy_fmt, M, N, K), dy, lddy, dy_fmt, xl, dW, dbias, M, N, K, stream);
+}
+
+// The route leod_linear_wgrad takes for this problem in the current precision mode, without launching anything: the code of wgrad_route
+// above (100 + T LDS-DMA, 200 + combo wide, 300 + cfg wgradw, 400 + 10 TN + TK wgrad16, 0 nothing to do, < 0 the error the call returns).
+// has_stats: stats, ln_w and ln_b are given; has_x2: x2 is given.  leod_linear_wgrad switches on the same value; it leaves a 100 + T route
+// only when no workspace is registered for its stream and none can be allocated (stream capture): register one (leod_set_workspace).
+LEOD_API int leod_linear_wgrad_route(int M, int N, int K, long lddy, long ldx, long ldx2, int K1, int dy_fmt, int x_fmt, int has_stats,
+                                     int has_x2) {
+    if (!wgrad_formats_ok(dy_fmt, x_fmt, has_stats != 0, has_stats != 0, has_x2 != 0)) return LEOD_ERR_ARG;
+    static const float given = 0.f;                  // a non-NULL address: wgrad_route tests stats / x2 for presence only
+    XRows xl{&given, ldx, has_stats ? &given : nullptr, has_stats ? &given : nullptr, has_stats ? &given : nullptr,
+             has_x2 ? &given : nullptr, ldx2, K1};
+    xl.set_mode(x_fmt);
+    return wgrad_route(xl, lddy, dy_fmt, M, N, K);
 }
 
 // n <= 4 Linear weight gradients of ONE row count M in one preparation launch, one contraction launch and one reduce launch (the LDS-DMA

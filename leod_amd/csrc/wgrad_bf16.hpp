@@ -509,11 +509,12 @@ static inline bool use_wgrad_wide(const XRows& xl, long lddy, int M, int N, int 
     if (xl.x2 && (xm != XM_ROWS || (xl.K1 % 4) || (xl.ld2 % 4))) return false;
     return wgrad_wide_combo(xl, N, K, dyfmt) != 0;
 }
-static inline int launch_wgrad_wide(const void* dy, long lddy, const XRows& xl, float* dW, long ldw, float* dbias,
-                                    int M, int N, int K, hipStream_t s, int dyfmt) {
+// combo: what wgrad_wide_combo returned for this problem (the router decides once and launches what it decided)
+static inline int launch_wgrad_wide(int combo, const void* dy, long lddy, const XRows& xl, float* dW, long ldw, float* dbias,
+                                    int M, int N, int K, hipStream_t s) {
 #define LEOD_WGW(TN, TK, NWN, NWK, RC, DYF, XM, OCC) \
     return launch_wgrad_wide_cfg<TN, TK, NWN, NWK, RC, DYF, XM, OCC>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s)
-    switch (wgrad_wide_combo(xl, N, K, dyfmt)) {
+    switch (combo) {
         case 1: LEOD_WGW(3, 3, 1, 1, 64, 0, XM_ROWS, 2);
         case 2: LEOD_WGW(12, 3, 4, 1, 32, 1, XM_LN, 4);
         case 3: LEOD_WGW(3, 12, 1, 4, 32, 0, XM_GELU16, 3);

@@ -381,15 +381,17 @@ static inline int launch_wgrad_dma_t(const void* dy, long lddy, const XRows& xl,
     const WgdHostProb h{dy, lddy, xl, dW, ldw, dbias, N, K, dyfmt};
     return launch_wgrad_dma_group_t<T, RC, NS>(1, &h, M, s);
 }
-static inline int launch_wgrad_dma(const void* dy, long lddy, const XRows& xl, float* dW, long ldw, float* dbias,
+// tile: what wgd_tile returned for this problem
+static inline int launch_wgrad_dma(int tile, const void* dy, long lddy, const XRows& xl, float* dW, long ldw, float* dbias,
                                    int M, int N, int K, hipStream_t s, int dyfmt) {
     // (192 x 192 tiles -- T = 12, one workgroup per CU, half the LDS-DMA bytes per output -- measured slower on 9 of the 10 shapes of
     // tools/kbench_wgrad_small.py: 593 vs 549 us summed; the chunk stream is not bound by DMA bytes, profiles/r06_d_wgrad_dma_kbench.txt)
     // 128 x 128 tiles: two ring slots of 64 rows (2 workgroups per CU) beat three slots of 32 or 64 rows and 64 x 64 tiles on every shape of
     // RVT-B (3597 vs 3703 / 4054 / 4392 us over the twenty launches of profiles/r06_f_wgrad_dma_1mpx_kbench.txt)
-    switch (wgd_tile(N, K)) {
+    switch (tile) {
         case 6: return launch_wgrad_dma_t<6, 64, 3>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
         case 8: return launch_wgrad_dma_t<8, 64, 2>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
-        default: return launch_wgrad_dma_t<4, 64, 3>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
+        case 4: return launch_wgrad_dma_t<4, 64, 3>(dy, lddy, xl, dW, ldw, dbias, M, N, K, s, dyfmt);
     }
+    return LEOD_ERR_ARG;
 }

@@ -502,6 +502,18 @@ def linear_wgrad(dy, x, dW, dbias=None, stats=None, ln_w=None, ln_b=None, x2=Non
         ev.record()
 
 
+def linear_wgrad_route(M, N, K, dy_fmt=0, x_fmt=0, K1=None, lddy=None, ldx=None, ldx2=None, has_stats=None) -> int:
+    """The kernel ``linear_wgrad`` runs for this problem in the current precision mode (``leod_linear_wgrad_route``; nothing is launched):
+    100 + tile LDS-DMA, 200 + combination wide kernel, 300 + configuration wgradw, 400 + 10 TN + TK wgrad16, 0 nothing to do, negative
+    the error code of the call.  dy_fmt / x_fmt as in ``leod_linear_wgrad``; K1 < K: X = [x | x2] with K1 columns from x; the strides
+    default to dense rows (N, K1, K - K1), has_stats to ``x_fmt == 1``."""
+    K1 = K if K1 is None else K1
+    x2 = K1 < K
+    return int(_l().leod_linear_wgrad_route(M, N, K, N if lddy is None else lddy, K1 if ldx is None else ldx,
+                                            (K - K1 if ldx2 is None else ldx2) if x2 else 0, K1, dy_fmt, x_fmt,
+                                            int(x_fmt == 1 if has_stats is None else has_stats), int(x2)))
+
+
 def linear_wgrad_group(problems) -> bool:
     """n <= 4 Linear weight gradients of one row count in ONE preparation / contraction / reduce launch (``leod_linear_wgrad_group``).
     problems: dicts with dy, x, dW, dbias and optionally stats + ln_w + ln_b (X = LayerNorm(x)) or gelu=True (x the fp16 pre-activation).
