@@ -185,6 +185,19 @@ int leod_linear_wgrad(const float* dy, long lddy, const float* x, long ldx, cons
  * (leod_set_workspace) and the answer is what runs. */
 int leod_linear_wgrad_route(int M, int N, int K, long lddy, long ldx, long ldx2, int K1, int dy_fmt, int x_fmt, int has_stats,
                             int has_x2);
+/* The same query for the nine Linear forward / input-gradient calls: which kernel the call runs in the current precision mode, or the
+ * negative error it returns (NULL pointers apart).  entry: 0 leod_ln_linear_fwd, 1 leod_linear_lsres_fwd, 2 leod_ln_linear_gelu16_fwd,
+ * 3 leod_ln_linear_bf16_fwd, 4 leod_linear_lsres_bf16_fwd, 5 leod_linear_lsres_gelu16_fwd, 6 leod_linear_dgrad, 7 leod_linear_dgrad_lnbwd,
+ * 8 leod_linear_dgrad_gelu16.  M, N, K as that call takes them; lda / ldo: row strides of its input rows (x, a, dy) and of the rows it
+ * stores; a16 / out16: its dy_fmt or dy_bf16 / dx_fmt or out_bf16 (0 where it has none); nsplit as leod_linear_dgrad; flags, the optional
+ * pointers that are given: 1 ln_w, 2 stats_out or stats, 4 kscale, 8 out_act or aux_u, 16 tout, 32 dx2, 64 colsum, 128 accumulate, 256 dres.
+ *   1000 + 100 KC + NTT   row-streaming kernel, contraction of 16 KC, slabs of NTT blocks of 16 columns
+ *   2000 + KC             narrow row-streaming kernel, contraction of 16 KC into 48 (KC 9, 12) or 96 (KC 18, 24) columns
+ *   3000 + NTW            persistent wide-tile kernel, workgroups of 64 NTW columns (NTW 3, 4)
+ *   4000 + 100 NT + KCH   LDS-staged kernel, NT blocks of 16 columns, K chunks of KCH (48, 64), two-phase row loader
+ *   5000 + 100 NT + KCH   the same with the plain row loader
+ *   6000 + 10 NT + KS     register-direct kernel, K split over KS waves (1, 4) */
+int leod_linear_route(int entry, int M, int N, int K, long lda, long ldo, int a16, int out16, int flags, int nsplit);
 
 /* LayerNorm over channels (eps 1e-5), maxvit.py:172-178 and its autograd. */
 int leod_layernorm_fwd(const float* x, const float* w, const float* b, float* y, float* stats, int M, int C, float eps,

@@ -959,12 +959,12 @@ __global__ __launch_bounds__(256) void gemm16_kernel(AL al, BL bl, EP ep, int M,
     ep.template run<NT, BL>(acc, bl, row0, nblk, lane, M);
 }
 
+// fewer than ~2 workgroups per CU and a long K loop: split K across the 4 waves of each workgroup
+static inline bool gemm16_ksplit(int M, int K, int nblocks_n) { return (long)cdiv(M, 64) * nblocks_n < 512 && K >= 128; }
 template <int NT, class AL, class BL, class EP>
 static inline int launch_gemm16(const AL& al, const BL& bl, const EP& ep, int M, int K, int nblocks_n, hipStream_t s) {
     if (M <= 0) return LEOD_OK;
-    // fewer than ~2 workgroups per CU and a long K loop: split K across the 4 waves of each workgroup
-    const bool ksplit = (long)cdiv(M, 64) * nblocks_n < 512 && K >= 128;
-    if (ksplit) {
+    if (gemm16_ksplit(M, K, nblocks_n)) {
         dim3 grid(cdiv(M, 16), nblocks_n);
         LEOD_BY_OPFMT_IF(bl_fwd<BL>::value, hipLaunchKernelGGL((gemm16_kernel<NT, 4, OF, AL, BL, EP>), grid, dim3(256), 0, s, al, bl, ep, M, K));
     } else {
@@ -980,7 +980,7 @@ static inline int launch_gemm16(const AL& al, const BL& bl, const EP& ep, int M,
 // 16 rows x 64 B.  Measured on MI355X that gather pattern (16 partial cache lines per instruction, 4x the line
 // requests of a contiguous stream) caps those kernels at ~1 TB/s, whereas row-contiguous 1 KiB wave loads stream at
 // 2.5-3 TB/s.  Here both operands are fetched with fully coalesced 16-byte loads (each thread owns fixed (row, k4)
-// slots), double-buffered through LDS, and read back in operand layout with conflict-free ds_read_b128.
+// slots), staged through ONE LDS buffer, and read back in operand layout with conflict-free ds_read_b128.
 // =================================================================================================
 // RW = 16-row fragments per wave (workgroup = 64*RW rows): RW = 2 halves the B-fragment LDS reads and the B staging per
 // output row -- the MFMA-bound shapes (RVT stages 3/4, 3x3 convs) were LDS-bandwidth limited at RW = 1 (every wave
@@ -991,8 +991,8 @@ static inline int launch_gemm16(const AL& al, const BL& bl, const EP& ep, int M,
 // distinct bank pairs.  Transposed weights (dgrad: W[k][n], n contiguous) are stored as [16 k][16 n] blocks in their natural
 // orientation (8-byte stores of 4 n; block stride 512 + 32 bytes keeps the 16-lane store groups conflict-free) and read back with
 // ds_read_b64_tr_b16, whose 16-lane groups return the [4 k][16 n] block column-wise: lane (i, q) gets W[4q..4q+3][n = i].
-template <int NT, int KCH, int NBUF, int RW, int BF, class AL, class BL, class EP>
-__global__ __launch_bounds__(256, NBUF == 1 ? (RW == 1 ? 4 : 3) : 2) void gemm_lds_kernel(AL al, BL bl, EP ep, int M, int K, int nblocks_n) {
+template <int NT, int KCH, int RW, int BF, class AL, class BL, class EP>
+__global__ __launch_bounds__(256, RW == 1 ? 4 : 3) void gemm_lds_kernel(AL al, BL bl, EP ep, int M, int K, int nblocks_n) {
     constexpr int BM = 64 * RW;
     // ds_read_b128 is serviced in 4 groups of 16 lanes, {0-3,12-15,20-27}, ...: rows {0-3,12-15} at k-offset 4q and rows
     // {4-11} at 4(q+1) share a group.  A row stride == 8 (mod 16) dwords puts the 16 starts on 16 distinct 4-bank slots
@@ -1011,11 +1011,11 @@ __global__ __launch_bounds__(256, NBUF == 1 ? (RW == 1 ? 4 : 3) : 2) void gemm_l
     constexpr int BSZ = BF ? (BL::kTrans ? ((KCH / 16) * NT * BST) / 2 : (BN * LD) / 2) : (BL::kTrans ? KCH * LDN : BN * LD);
     constexpr int LDO = 64;                          // accumulator transposition tile of the row-layout epilogue (aliases A/B);
                                                      // 256-byte rows: the (row q, 16-byte column c4) reads are conflict-free
-    constexpr int OPS = NBUF * (ASZ + BSZ);
+    constexpr int OPS = ASZ + BSZ;
     constexpr int SMEM = OPS >= 64 * LDO ? OPS : 64 * LDO;      // the epilogue tile must fit in the operand buffers
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
-    float (*sA)[ASZ] = reinterpret_cast<float (*)[ASZ]>(smem);
-    float (*sB)[BSZ] = reinterpret_cast<float (*)[BSZ]>(smem + NBUF * ASZ);
+    float* sA = smem;
+    float* sB = smem + ASZ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 15, q = lane >> 4;
     // XCD-aware 1-D grid: consecutive workgroup ids go round-robin to the 8 XCDs (each with its own L2).  All n-blocks of
@@ -1086,20 +1086,20 @@ __global__ __launch_bounds__(256, NBUF == 1 ? (RW == 1 ? 4 : 3) : 2) void gemm_l
             }
         }
     };
-    auto stash = [&](int buf) {
+    auto stash = [&]() {
         if constexpr (BF) {
-            unsigned short* __restrict__ a16 = reinterpret_cast<unsigned short*>(sA[buf]);
-            unsigned short* __restrict__ b16 = reinterpret_cast<unsigned short*>(sB[buf]);
+            unsigned short* __restrict__ a16 = reinterpret_cast<unsigned short*>(sA);
+            unsigned short* __restrict__ b16 = reinterpret_cast<unsigned short*>(sB);
 #pragma unroll
             for (int p = 0; p < RA; ++p) if (aok[p]) *reinterpret_cast<s4*>(a16 + al_off[p]) = pack16<BF>(ra[p]);
 #pragma unroll
             for (int p = 0; p < RB; ++p) if (bok[p]) *reinterpret_cast<s4*>(b16 + bl_off[p]) = bl_is16<BL>::value ? shadow_s4(rb[p]) : pack16_raw<BF>(rb[p]);
         } else {
 #pragma unroll
-            for (int p = 0; p < RA; ++p) if (aok[p]) *reinterpret_cast<f4*>(&sA[buf][al_off[p]]) = ra[p];
+            for (int p = 0; p < RA; ++p) if (aok[p]) *reinterpret_cast<f4*>(&sA[al_off[p]]) = ra[p];
 #pragma unroll
             for (int p = 0; p < RB; ++p) if (bok[p]) {
-                *reinterpret_cast<f4*>(&sB[buf][bl_off[p]]) = rb[p];
+                *reinterpret_cast<f4*>(&sB[bl_off[p]]) = rb[p];
             }
         }
     };
@@ -1111,18 +1111,17 @@ __global__ __launch_bounds__(256, NBUF == 1 ? (RW == 1 ? 4 : 3) : 2) void gemm_l
     const int nch = (K + KCH - 1) / KCH;
     fetch(0);
     finish(0);
-    stash(0);
+    stash();
     __syncthreads();
     const int aoff = (16 * RW * wave + i) * LD + 4 * q;                            // wave owns rows 16*RW*wave ..
     const int boff = BL::kTrans ? (4 * q) * LDN + i : i * LD + 4 * q;
     for (int ch = 0; ch < nch; ++ch) {
-        const int buf = NBUF == 1 ? 0 : (ch & 1);
         const bool more = ch + 1 < nch;
         if (more) fetch((ch + 1) * KCH);                      // next chunk's global loads fly under this chunk's MFMAs
         if constexpr (BF) {
             typedef __attribute__((address_space(3))) s4 lds_s4;
-            const unsigned short* __restrict__ pa = reinterpret_cast<const unsigned short*>(sA[buf]) + aoff;
-            const unsigned short* __restrict__ pb = reinterpret_cast<const unsigned short*>(sB[buf]) +
+            const unsigned short* __restrict__ pa = reinterpret_cast<const unsigned short*>(sA) + aoff;
+            const unsigned short* __restrict__ pb = reinterpret_cast<const unsigned short*>(sB) +
                                                     (BL::kTrans ? (4 * q + (i >> 2)) * 16 + 4 * (i & 3) : boff);
 #pragma unroll
             for (int c = 0; c < KCH / 16; ++c) {
@@ -1139,8 +1138,8 @@ __global__ __launch_bounds__(256, NBUF == 1 ? (RW == 1 ? 4 : 3) : 2) void gemm_l
                 }
             }
         } else {
-        const float* __restrict__ pa = sA[buf] + aoff;
-        const float* __restrict__ pb = sB[buf] + boff;
+        const float* __restrict__ pa = sA + aoff;
+        const float* __restrict__ pb = sB + boff;
 #pragma unroll
         for (int c = 0; c < KCH / 16; ++c) {
             f4 av[RW];
@@ -1162,13 +1161,10 @@ __global__ __launch_bounds__(256, NBUF == 1 ? (RW == 1 ? 4 : 3) : 2) void gemm_l
             }
         }
         }
-        if (NBUF > 1) {
-            if (more) { finish((ch + 1) * KCH); stash(buf ^ 1); }
-            __syncthreads();
-        } else if (more) {                                    // single LDS buffer (half the LDS -> twice the resident
+        if (more) {                                           // single LDS buffer (half the LDS -> twice the resident
             finish((ch + 1) * KCH);
             __syncthreads();                                  // workgroups): everyone done reading, then refill
-            stash(0);
+            stash();
             __syncthreads();
         }
     }
@@ -1253,6 +1249,7 @@ template <class BL> static inline typename bl_shadow_type<BL>::type bl_as16(cons
     return b;
 }
 
+static inline int gemm_lds_kch(int K) { return K % 48 == 0 ? 48 : 64; }       // K chunk of gemm_lds_kernel
 template <int NT, int RW, class AL, class BL, class EP>
 static inline int launch_gemm_lds_rw(const AL& al, const BL& bl, const EP& ep, int M, int K, int nblocks_n, hipStream_t s) {
 #ifdef LEOD_SHADOW_KERNELS
@@ -1262,14 +1259,12 @@ static inline int launch_gemm_lds_rw(const AL& al, const BL& bl, const EP& ep, i
 #endif
     dim3 grid(cdiv(cdiv(M, 64 * RW), 8) * 8 * nblocks_n);
     // single LDS buffer + register prefetch everywhere: residency (3-6 workgroups per CU) hides the two barriers per chunk
-    // better than a double buffer at 2-3 workgroups per CU does (measured)
-    static const int nbuf = 1;
-    (void)nbuf;                                      // the double-buffered variant is no longer instantiated (never faster, see above)
+    // better than a double buffer at 2-3 workgroups per CU does (measured: the double buffer was never faster)
     // (96-wide chunks in the 16-bit modes, measured: 38.2 vs 34.2 ms per step on -> off; not instantiated)
-    if (K % 48 == 0) {
-        LEOD_BY_OPFMT_IF(bl_fwd<BL>::value, hipLaunchKernelGGL((gemm_lds_kernel<NT, 48, 1, RW, OF, AL, BL, EP>), grid, dim3(256), 0, s, al, bl, ep, M, K, nblocks_n));
+    if (gemm_lds_kch(K) == 48) {
+        LEOD_BY_OPFMT_IF(bl_fwd<BL>::value, hipLaunchKernelGGL((gemm_lds_kernel<NT, 48, RW, OF, AL, BL, EP>), grid, dim3(256), 0, s, al, bl, ep, M, K, nblocks_n));
     } else {
-        LEOD_BY_OPFMT_IF(bl_fwd<BL>::value, hipLaunchKernelGGL((gemm_lds_kernel<NT, 64, 1, RW, OF, AL, BL, EP>), grid, dim3(256), 0, s, al, bl, ep, M, K, nblocks_n));
+        LEOD_BY_OPFMT_IF(bl_fwd<BL>::value, hipLaunchKernelGGL((gemm_lds_kernel<NT, 64, RW, OF, AL, BL, EP>), grid, dim3(256), 0, s, al, bl, ep, M, K, nblocks_n));
     }
     return leod_launch_status();
 }
@@ -1279,47 +1274,67 @@ static inline int launch_gemm_lds(const AL& al, const BL& bl, const EP& ep, int 
     // resident workgroups, two epilogue rounds), so only RW = 1 is instantiated.
     return launch_gemm_lds_rw<NT, 1>(al, bl, ep, M, K, nblocks_n, s);
 }
-#include "gemm_bf16.hpp"
-// plain-row A operands: the hot mode combinations of the wide GEMMs (NT >= 3) run on the two-phase loader ALRowsM
+#include "gemm_bf16.hpp"           // needs the loaders, epilogues and shadow helpers above; the launchers below need its wide kernel
+
+// Plain-row A operands (ALRows: the Linear layers, the 1x1 convs): which LDS-staged kernel runs a problem that use_gemm_lds() accepts.
+// trans: the weights are read transposed (BLTrans, dgrad); lsres: EpLsRes epilogue (else EpStore); fmt: RowFmt of the A rows; ln: LayerNorm
+// on load, stats: with precomputed (mean, rstd); ks: per-k scale; gelu_grad: EpStore multiplies by gelu'(aux).  N output columns, NT the
+// caller's column tiles.  Launches nothing; rows_gemm_kind(al, bl, ep, ..) below reads the same facts off the launch arguments.
+enum RowsGemm : int { RG_WIDE = 3000 /* + NTW 3 | 4: gemm_wide_bf16_kernel */, RG_TWO_PHASE = 4000 /* gemm_lds_kernel on ALRowsM */, RG_PLAIN = 5000 /* on ALRows */ };
+// the (format, LayerNorm, scale) combinations the two kernels are instantiated for: the LEOD_WIDE / LEOD_ALM lists of launch_gemm_lds
+static inline bool rows_wide_has(bool trans, bool lsres, int fmt, bool ln, bool ks) {
+    if (!trans && !lsres) return fmt == FMT_F32 && !ks;
+    if (!trans) return !ln && !ks && fmt != FMT_BF16;
+    return !lsres && !ln && (fmt == FMT_F32 || (fmt == FMT_BF16 && !ks));
+}
+static inline bool rows_two_phase_has(int fmt, bool ln, bool ks) { return ln ? fmt == FMT_F32 && !ks : (!ks || fmt == FMT_F32 || fmt == FMT_BF16); }
+static inline int rows_gemm_kind(int M, int K, int N, int NT, bool trans, bool lsres, int fmt, bool ln, bool stats, bool ks, bool gelu_grad) {
+    // precision mode bf16, >= 144 output columns: the persistent 128 x 192 / 256 wide tiles (gemm_bf16.hpp) win where the main loop dominates
+    // (LayerNorm on load, contractions of >= 2 N); short contractions into wide outputs are bound by their epilogue traffic, which the many
+    // small workgroups of gemm_lds_kernel overlap better (tools/kbench_gemm.py; routing every covered shape here was slower).
+    // (round 5, tools/kbench_gemm.py graph-timed, profiles/r05_j_gemm_wide_routing_ab.txt) launches of <= 60 k rows (stages 3-4): also the
+    // square projections (proj + LayerScale, its dgrad: 24 -> 16-22 us) and the plain x projection of the ConvLSTM (85 / 75 -> 70 / 67 us); NOT
+    // the dgrad of fc2 through GELU (short contraction, wide output, heavy epilogue: 134 -> 191 us on the wide tiles)
+    const bool small_ok = M <= 60000 && (K >= N || (!trans && !lsres)) && !gelu_grad;
+    if ((!ln || stats) && (ln || K >= 2 * N || small_ok) && rows_wide_has(trans, lsres, fmt, ln, ks))
+        if (const int ntw = gemm_wide_ntw(M, N, K)) return RG_WIDE + ntw;
+    // the hot mode combinations of the wide GEMMs (NT >= 3) run on the two-phase loader ALRowsM
+    return (NT >= 3 && !(K & 3) && K >= 4 && (!ln || stats) && rows_two_phase_has(fmt, ln, ks)) ? RG_TWO_PHASE : RG_PLAIN;
+}
+template <class BL, class EP>
+static inline int rows_gemm_kind(const ALRows& al, const BL& bl, const EP& ep, int M, int K, int NT) {
+    bool gelu_grad = false;
+    if constexpr (std::is_same<EP, EpStore>::value) gelu_grad = ep.act == ACT_MUL_GELU_GRAD;
+    return rows_gemm_kind(M, K, bl.N, NT, BL::kTrans, std::is_same<EP, EpLsRes>::value, al.fmt, al.ln_w != nullptr, al.stats_in != nullptr,
+                          al.kscale != nullptr, gelu_grad);
+}
+// ... and the switch that launches what rows_gemm_kind decided
 template <int NT, class BL, class EP>
-static inline int launch_gemm_lds(const ALRows& al, const BL& bl, const EP& ep, int M, int K, int nblocks_n, hipStream_t s) {
-    static const int two_phase = 1;
-    // precision mode bf16, Linear forward / dgrad with >= 144 output columns: the 128 x 192 / 256 wide-tile kernel (gemm_bf16.hpp)
-    if constexpr ((std::is_same<BL, BLRows>::value || std::is_same<BL, BLTrans>::value) &&
-                  (std::is_same<EP, EpStore>::value || std::is_same<EP, EpLsRes>::value)) {
-        const bool ln = al.ln_w != nullptr, ks = al.kscale != nullptr;
-        // the persistent wide tiles win where the main loop dominates (LayerNorm on load, contractions of >= 2 N); short contractions
-        // into wide outputs are bound by their epilogue traffic, which the many small workgroups of gemm_lds_kernel overlap better
-        // (tools/kbench_gemm.py; wide_mode = 2 would route every covered shape here)
-        constexpr int wide_mode = 1;
-        // (round 5, tools/kbench_gemm.py graph-timed, profiles/r05_j_gemm_wide_routing_ab.txt) launches of <= 60 k rows (stages 3-4): also the
-        // square projections (proj + LayerScale, its dgrad: 24 -> 16-22 us) and the plain x projection of the ConvLSTM (85 / 75 -> 70 / 67 us); NOT
-        // the dgrad of fc2 through GELU (short contraction, wide output, heavy epilogue: 134 -> 191 us on the wide tiles)
-        bool small_ok = M <= 60000 && (K >= bl.N || (std::is_same<BL, BLRows>::value && std::is_same<EP, EpStore>::value));
-        if constexpr (std::is_same<EP, EpStore>::value) small_ok = small_ok && ep.act != ACT_MUL_GELU_GRAD;
-        const int ntw = ((!ln || al.stats_in) && (wide_mode >= 2 || ln || K >= 2 * bl.N || small_ok)) ? gemm_wide_ntw(M, bl.N, K) : 0;
-        if (ntw) {
+static inline int launch_gemm_lds(int kind, const ALRows& al, const BL& bl, const EP& ep, int M, int K, int nblocks_n, hipStream_t s) {
+    static_assert((std::is_same<BL, BLRows>::value || std::is_same<BL, BLTrans>::value) && (std::is_same<EP, EpStore>::value || std::is_same<EP, EpLsRes>::value),
+                  "plain-row problems are Linear layers and 1x1 convs");
+    const bool ln = al.ln_w != nullptr, ks = al.kscale != nullptr;
+    if (kind >= RG_WIDE && kind < RG_TWO_PHASE) {
 #define LEOD_WIDE(F, L, S) { ALRowsM<F, L, S> am; static_cast<ALRows&>(am) = al;                                                     \
-                             return ntw == 3 ? launch_gemm_wide<3>(am, bl, ep, M, K, bl.N, s) : launch_gemm_wide<4>(am, bl, ep, M, K, bl.N, s); }
-            constexpr bool rows = std::is_same<BL, BLRows>::value, store = std::is_same<EP, EpStore>::value;
-            if constexpr (rows && store) {                  // LN -> qkv / fc1, plain x projection of the ConvLSTM
-                if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
-                if (al.fmt == FMT_F32 && ln && !ks) LEOD_WIDE(FMT_F32, true, false)
-            } else if constexpr (rows && !store) {          // proj / fc2 + LayerScale + residual (fc2: gelu of the fp16 pre-activation)
-                if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
-                if (al.fmt == FMT_F16PRE && !ln && !ks) LEOD_WIDE(FMT_F16PRE, false, false)
-                if (al.fmt == FMT_F16 && !ln && !ks) LEOD_WIDE(FMT_F16, false, false)
-            } else if constexpr (!rows && store) {          // dgrads: fp32 / bf16 gradient rows, optional LayerScale factor
-                if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
-                if (al.fmt == FMT_F32 && !ln && ks) LEOD_WIDE(FMT_F32, false, true)
-                if (al.fmt == FMT_BF16 && !ln && !ks) LEOD_WIDE(FMT_BF16, false, false)
-            }
-#undef LEOD_WIDE
+                             return kind == RG_WIDE + 3 ? launch_gemm_wide<3>(am, bl, ep, M, K, bl.N, s) : launch_gemm_wide<4>(am, bl, ep, M, K, bl.N, s); }
+        constexpr bool rows = std::is_same<BL, BLRows>::value, store = std::is_same<EP, EpStore>::value;
+        if constexpr (rows && store) {                  // LN -> qkv / fc1, plain x projection of the ConvLSTM
+            if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
+            if (al.fmt == FMT_F32 && ln && !ks) LEOD_WIDE(FMT_F32, true, false)
+        } else if constexpr (rows && !store) {          // proj / fc2 + LayerScale + residual (fc2: gelu of the fp16 pre-activation)
+            if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
+            if (al.fmt == FMT_F16PRE && !ln && !ks) LEOD_WIDE(FMT_F16PRE, false, false)
+            if (al.fmt == FMT_F16 && !ln && !ks) LEOD_WIDE(FMT_F16, false, false)
+        } else if constexpr (!rows && store) {          // dgrads: fp32 / bf16 gradient rows, optional LayerScale factor
+            if (al.fmt == FMT_F32 && !ln && !ks) LEOD_WIDE(FMT_F32, false, false)
+            if (al.fmt == FMT_F32 && !ln && ks) LEOD_WIDE(FMT_F32, false, true)
+            if (al.fmt == FMT_BF16 && !ln && !ks) LEOD_WIDE(FMT_BF16, false, false)
         }
+#undef LEOD_WIDE
+        return LEOD_ERR_ARG;                            // rows_wide_has() and the list above disagree
     }
     if constexpr (NT >= 3) {
-        const bool ln = al.ln_w != nullptr, ks = al.kscale != nullptr;
-        if (two_phase && !(K & 3) && K >= 4 && (!ln || al.stats_in)) {
+        if (kind == RG_TWO_PHASE) {
 #define LEOD_ALM(F, L, S) { ALRowsM<F, L, S> am; static_cast<ALRows&>(am) = al; return launch_gemm_lds_rw<NT, 1>(am, bl, ep, M, K, nblocks_n, s); }
             if (al.fmt == FMT_F32 && !ln && !ks) LEOD_ALM(FMT_F32, false, false)
             if (al.fmt == FMT_F32 && ln && !ks) LEOD_ALM(FMT_F32, true, false)
@@ -1329,9 +1344,10 @@ static inline int launch_gemm_lds(const ALRows& al, const BL& bl, const EP& ep, 
             if (al.fmt == FMT_F16PRE && !ln && !ks) LEOD_ALM(FMT_F16PRE, false, false)
             if (al.fmt == FMT_F16 && !ln && !ks) LEOD_ALM(FMT_F16, false, false)
 #undef LEOD_ALM
+            return LEOD_ERR_ARG;                        // rows_two_phase_has() and the list above disagree
         }
     }
-    return launch_gemm_lds_rw<NT, 1>(al, bl, ep, M, K, nblocks_n, s);
+    return kind == RG_PLAIN ? launch_gemm_lds_rw<NT, 1>(al, bl, ep, M, K, nblocks_n, s) : LEOD_ERR_ARG;
 }
 // enough 64-row workgroups to fill the chip; smaller problems stay on the register-direct kernels (K-split)
 static inline bool use_gemm_lds(int M, int nblocks_n) { return (long)cdiv(M, 64) * nblocks_n >= 256 && M >= 2048; }

@@ -78,7 +78,7 @@ LEOD_API int leod_conv_nhwc_fwd(const float* x, const float* w, const float* bia
     if (ks == 1 && stride == 1 && pad == 0) {
         ALRows al{}; al.x = x; al.ld = Cin; al.K = Cin;
         DISPATCH_NT(nt, { BLRows bl{w, (long)Cin, N, NT};
-                          rc = lds ? launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream)
+                          rc = lds ? launch_gemm_lds<NT>(rows_gemm_kind(al, bl, ep, M, K, NT), al, bl, ep, M, K, cdiv(N, 16 * NT), stream)
                                    : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
     } else {
         ALConvNHWC al{x, H, W, Cin, Ho, Wo, ks, stride, pad};
@@ -323,7 +323,7 @@ LEOD_API int leod_conv_nhwc_dgrad(const float* dy, const float* w, float* dx, in
     if (ks == 1 && stride == 1 && pad == 0) {
         ALRows al{}; al.x = dy; al.ld = N; al.K = N;
         DISPATCH_NT(nt, { BLTrans bl{w, (long)Cin, Cin, NT};
-                          rc = lds ? launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream)
+                          rc = lds ? launch_gemm_lds<NT>(rows_gemm_kind(al, bl, ep, M, K, NT), al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream)
                                    : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream); });
     } else {
         ALConvT al{dy, H, W, Ho, Wo, N, ks, stride, pad};

@@ -9,47 +9,35 @@ LEOD_API int leod_ln_linear_fwd(const float* x, long ldx, const float* ln_w, con
                                 const float* W, const float* bias, float* out, float* out_act, float* stats_out,
                                 int M, int N, int K, hipStream_t stream) {
     LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
-    if (!x || !W || !out || (K & 3) || (ldx & 3)) return LEOD_ERR_ARG;
-    ALRows al{}; al.x = x; al.ld = ldx; al.ln_w = ln_w; al.ln_b = ln_b; al.eps = eps; al.stats_out = stats_out; al.K = K;
-    EpStore ep = ep_store(out, N, N);
-    ep.bias = bias;
-    if (out_act) { ep.act = ACT_GELU_DUAL; ep.out2 = out_act; ep.ld2 = N; }
-    const int nt = pick_nt(N);
-    int rc = LEOD_OK;
-    if (const int slab = ((!ln_w || stats_out) && ldx == K) ? rowstream_slab(M, N, K) : 0) {
-        float* st = ln_w ? stats_out : nullptr;                 // the kernel derives (mean, rstd) itself and leaves them here
-#define RS_CASE(KCV, NTTV)                                                                                                         \
-        if (K == 16 * KCV && slab == NTTV)                                                                                         \
-            return out_act ? launch_rowstream48<KCV, NTTV, true>(x, ldx, st, ln_w, ln_b, eps, W, bias, out, out_act, M, N, stream)   \
-                           : launch_rowstream48<KCV, NTTV, false>(x, ldx, st, ln_w, ln_b, eps, W, bias, out, nullptr, M, N, stream);
-        RS_CASE(3, 9) RS_CASE(3, 12) RS_CASE(6, 9) RS_CASE(6, 8) RS_CASE(4, 12) RS_CASE(4, 8)
-#undef RS_CASE
-    }
-    if (use_gemm_lds(M, cdiv(N, 16 * nt)) && (!ln_w || stats_out)) {
-        if (ln_w) { rc = launch_row_stats(x, ldx, stats_out, M, K, eps, stream); if (rc) return rc; al.stats_in = stats_out; }
-        DISPATCH_NT(nt, { BLRows bl{W, (long)K, N, NT}; rc = launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-        return rc;
-    }
-    DISPATCH_NT(nt, { BLRows bl{W, (long)K, N, NT}; rc = launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-    return rc;
+    if (!x || !W || !out) return LEOD_ERR_ARG;
+    const LinearProb p = linear_prob(LE_LN_LINEAR, M, N, K, ldx, N, 0, 0, (ln_w ? LF_LN : 0) | (stats_out ? LF_STATS : 0) | (out_act ? LF_AUX : 0), 0);
+    LinearArgs a{}; a.a = x; a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.W = W; a.bias = bias; a.out = out; a.ldo = N; a.out2 = out_act; a.ld2 = N;
+    a.stats = stats_out;
+    return launch_linear<LE_LN_LINEAR>(linear_route(p), p, a, stream);
 }
 
 // t = a @ W^T + bias ; tout = t (optional) ; out = res + gamma * t        (maxvit.py:268-269, LayerScale :51-53)
 LEOD_API int leod_linear_lsres_fwd(const float* a, const float* W, const float* bias, const float* gamma,
                                    const float* res, float* out, float* tout, int M, int N, int K, hipStream_t stream) {
     LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
-    if (!a || !W || !res || !out || (K & 3)) return LEOD_ERR_ARG;
-    ALRows al{}; al.x = a; al.ld = K; al.K = K;
-    EpLsRes ep{out, tout, res, bias, gamma, (long)N, N};
-    const int nt = pick_nt(N);
-    int rc = LEOD_OK;
-    if (!tout && use_rowstream_narrow(M, K, N)) return launch_rowstream_narrow<0>(a, W, bias, gamma, res, out, M, K, stream);
-    if (use_gemm_lds(M, cdiv(N, 16 * nt))) {
-        DISPATCH_NT(nt, { BLRows bl{W, (long)K, N, NT}; rc = launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-        return rc;
-    }
-    DISPATCH_NT(nt, { BLRows bl{W, (long)K, N, NT}; rc = launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-    return rc;
+    if (!a || !W || !res || !out) return LEOD_ERR_ARG;
+    const LinearProb p = linear_prob(LE_LSRES, M, N, K, K, N, 0, 0, tout ? LF_TOUT : 0, 0);
+    LinearArgs g{}; g.a = a; g.W = W; g.bias = bias; g.gamma = gamma; g.res = res; g.out = out; g.ldo = N; g.out2 = tout;
+    return launch_linear<LE_LSRES>(linear_route(p), p, g, stream);
+}
+
+// The kernel one of the nine Linear forward / dgrad entries runs for a problem in the current precision mode, without launching anything:
+// the code of linear_route (linear_common.hpp: 1000 + 100 KC + NTT rowstream48, 2000 + KC rowstream_narrow, 3000 + NTW wide tile,
+// 4000 / 5000 + 100 NT + KCH LDS-staged with the two-phase / plain loader, 6000 + 10 NT + KS gemm16, < 0 the error the call returns).
+// entry: 0 ln_linear_fwd, 1 linear_lsres_fwd, 2 ln_linear_gelu16_fwd, 3 ln_linear_bf16_fwd, 4 linear_lsres_bf16_fwd,
+// 5 linear_lsres_gelu16_fwd, 6 linear_dgrad, 7 linear_dgrad_lnbwd, 8 linear_dgrad_gelu16.  M, N, K as the entry takes them; lda / ldo:
+// strides of the A rows (x, a, dy) and of the stored rows; a16 / out16: dy_fmt | dy_bf16 / dx_fmt | out_bf16; flags: 1 ln_w, 2 stats_out |
+// stats, 4 kscale, 8 out_act | aux_u, 16 tout, 32 dx2, 64 colsum, 128 accumulate, 256 dres.  The entries switch on the same value.
+LEOD_API int leod_linear_route(int entry, int M, int N, int K, long lda, long ldo, int a16, int out16, int flags, int nsplit) {
+    if (entry < 0 || entry >= LE_COUNT) return LEOD_ERR_ARG;
+    if (kLinearEntry[entry].dgrad) return linear_route(linear_prob(entry, M, N, K, lda, ldo, a16, out16, flags, nsplit));
+    LeodFwdScope fwd_scope;
+    return linear_route(linear_prob(entry, M, N, K, lda, ldo, a16, out16, flags, nsplit));
 }
 
 // Fused ConvLSTM cell (models/layers/rnn.py:37-70, dws_conv=False): gates = [x | h_prev] @ W[4C,2C]^T + b,

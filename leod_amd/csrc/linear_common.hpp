@@ -465,17 +465,6 @@ static inline bool use_rowstream_narrow(int M, int Kc, int Nout) {
 static inline bool use_rowstream_narrow96(int M, int Kc, int Nout) {
     return leod_precision() == 1 && M >= 16384 && Nout == 96 && (Kc == 288 || Kc == 384);
 }
-template <int MODE>
-static int launch_rowstream_narrow(const float* x, const float* W, const float* bias, const float* gamma, const float* res,
-                                   float* out, int M, int Kc, hipStream_t s) {
-    const int grid = min(cdiv(cdiv(M, 16), 4), 256 * 2);
-    LEOD_BY_OPFMT_IF(MODE == 0, {
-        if (Kc == 192) hipLaunchKernelGGL((rowstream_narrow_kernel<12, MODE, OF>), dim3(grid), dim3(256), 0, s, x, W, bias, gamma, res, out, M);
-        else hipLaunchKernelGGL((rowstream_narrow_kernel<9, MODE, OF>), dim3(grid), dim3(256), 0, s, x, W, bias, gamma, res, out, M);
-    });
-    return leod_launch_status();
-}
-
 // (K, N) -> column tiles per slab; 0 = shape not covered.  K = 48: the whole N (9 / 12 tiles); K = 96: slabs of 9 (N = 288) or
 // 8 (N = 384) tiles, so that weights + wave tiles of two workgroups fit the 160 KB of a CU
 static inline int rowstream_slab(int M, int N, int K) {
@@ -485,33 +474,223 @@ static inline int rowstream_slab(int M, int N, int K) {
     if (K == 64) return N == 192 ? 12 : (N == 256 ? 8 : 0);      // RVT-B stage 1 (qkv whole, fc1 in two slabs)
     return 0;
 }
-template <int KC, int NTT, bool ACT>
-static int launch_rowstream48(const float* x, long ldx, float* stats, const float* ln_w, const float* ln_b, float eps, const float* W,
-                              const float* bias, float* out, float* out2, int M, int N, hipStream_t s) {
+// the grids of the two streaming kernels, for every launch of them
+static inline dim3 rowstream48_grid(int KC, int NTT, int M, int Nout) {
     const int per_cu = (KC == 3 && NTT <= 9) ? 3 : 2;        // resident workgroups per CU (registers / LDS): one wave of them
-    const int slabs = N / (16 * NTT);
-    const int gx = min(cdiv(cdiv(M, 16), 4), max(8, (256 * per_cu / slabs) & ~7));   // multiple of 8: slabs of a row range share an XCD
-    const dim3 grid(gx, slabs);
-    LEOD_BY_OPFMT({
-        if (stats) hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, true, ACT, 0, OF>), grid, dim3(256), 0, s, x, ldx, stats, ln_w, ln_b, eps, W, bias, out, out2, M, N);
-        else hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, false, ACT, 0, OF>), grid, dim3(256), 0, s, x, ldx, stats, ln_w, ln_b, eps, W, bias, out, out2, M, N);
-    });
-    return leod_launch_status();
+    const int slabs = Nout / (16 * NTT);
+    return dim3(min(cdiv(cdiv(M, 16), 4), max(8, (256 * per_cu / slabs) & ~7)), slabs);   // x a multiple of 8: slabs of a row range share an XCD
+}
+static inline dim3 rowstream_narrow_grid(int M, int NTN) {       // one 16-row tile per wave; NTN = 3: 4 waves, two workgroups per CU, 6: 8 waves, one
+    return dim3(NTN == 3 ? min(cdiv(cdiv(M, 16), 4), 256 * 2) : min(cdiv(cdiv(M, 16), 8), 256));
 }
 
-template <int KC, int NTT>
-static int launch_rowstream_dgrad(const float* dy, long lddy, const float* kscale, const float* W, const float* aux_u, float* dx,
-                                  int M, int Nout, hipStream_t s) {
-    const int slabs = Nout / (16 * NTT);
-    const int gx = min(cdiv(cdiv(M, 16), 4), max(8, (256 * 2 / slabs) & ~7));
-    const dim3 grid(gx, slabs);
-    float* aux = const_cast<float*>(aux_u);
-    if (leod_precision() == 1) {
-        if (aux_u) hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, false, false, 2, 1>), grid, dim3(256), 0, s, dy, lddy, nullptr, kscale, nullptr, 0.f, W, nullptr, dx, aux, M, Nout);
-        else hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, false, false, 1, 1>), grid, dim3(256), 0, s, dy, lddy, nullptr, kscale, nullptr, 0.f, W, nullptr, dx, aux, M, Nout);
-        return leod_launch_status();
+// ---------------------------------------------------------------------------------------------------------------------
+// Forward and input-gradient entry points of the Linear layers: one description (LinearProb), one router (linear_route), one launch
+// switch (launch_linear).  What differs between the entry points is the data of kLinearEntry.
+// ---------------------------------------------------------------------------------------------------------------------
+enum LinearEntry : int { LE_LN_LINEAR = 0, LE_LSRES, LE_LN_GELU16, LE_LN_BF16, LE_LSRES_BF16, LE_LSRES_GELU16, LE_DGRAD, LE_DGRAD_LNBWD, LE_DGRAD_GELU16, LE_COUNT };
+constexpr unsigned rs_bit(int KC, int NTT) { return 1u << ((KC == 3 ? 0 : KC == 6 ? 2 : 4) + (NTT == 9 || (KC == 4 && NTT == 12) ? 0 : 1)); }
+constexpr unsigned kRsFc1 = rs_bit(3, 12) | rs_bit(6, 8) | rs_bit(4, 8), kRsQkv = rs_bit(3, 9) | rs_bit(6, 9) | rs_bit(4, 12);
+struct LinearEntryInfo {
+    bool dgrad, lsres;              // reads W[N][K] transposed (BLTrans) | EpLsRes epilogue (else EpStore)
+    int kc_mask, lda_mask;          // alignment of the contraction length and the A row stride: LEOD_ERR_ARG
+    int needs16;                    // what the entry returns in precision mode f32 (0: it runs there)
+    unsigned rs_pairs;              // the (KC, NTT) pairs of rowstream48_kernel it is instantiated for
+    bool rs_commits, rs_ln_only;    // a shape rowstream_slab covers never tries the GEMMs | only with LayerNorm
+    bool narrow, narrow96, generic16, gemm16;   // rowstream_narrow 48 / 96 columns; 16-bit store: widths % 4; register-direct gemm16 (else refuse)
+};
+constexpr LinearEntryInfo kLinearEntry[LE_COUNT] = {
+    /* leod_ln_linear_fwd           */ {false, false, 3, 3, 0, kRsFc1 | kRsQkv, false, false, false, false, false, true},
+    /* leod_linear_lsres_fwd        */ {false, true, 3, 0, 0, 0, false, false, true, false, false, true},
+    /* leod_ln_linear_gelu16_fwd    */ {false, false, 0, 0, LEOD_ERR_UNSUPPORTED, kRsFc1, true, false, false, false, true, false},
+    /* leod_ln_linear_bf16_fwd      */ {false, false, 0, 0, LEOD_ERR_UNSUPPORTED, kRsQkv, true, true, false, false, true, false},
+    /* leod_linear_lsres_bf16_fwd   */ {false, true, 7, 0, LEOD_ERR_ARG, 0, false, false, false, false, false, false},
+    /* leod_linear_lsres_gelu16_fwd */ {false, true, 3, 0, LEOD_ERR_ARG, 0, false, false, true, true, false, true},
+    /* leod_linear_dgrad            */ {true, false, 3, 3, 0, kRsFc1, false, false, true, false, false, true},
+    /* leod_linear_dgrad_lnbwd      */ {true, false, 0, 0, 0, 0, false, false, true, true, false, false},
+    /* leod_linear_dgrad_gelu16     */ {true, false, 0, 0, LEOD_ERR_ARG, kRsFc1, true, false, false, false, true, false},
+};
+
+// A forward or input-gradient problem, fully described: out[M, nout] = A[M, kc] (x) W, W[nout][kc] forward, W[kc][nout] dgrad.
+struct LinearProb {
+    int entry;                      // LinearEntry
+    int M, kc, nout;                // rows, contraction length, output columns
+    int a_fmt; long lda; bool a_dense;          // RowFmt of the A rows, their stride, lda == kc
+    bool ln, stats;                 // LayerNorm on load | (mean, rstd) can be had (stats_out of a forward, the saved ones of a backward)
+    bool kscale;
+    int act, aux_fmt, out_fmt;      // ACT_NONE | ACT_GELU_DUAL | ACT_MUL_GELU_GRAD, RowFmt of aux and of the stored rows
+    bool tout;                      // EpLsRes: t is wanted too
+    bool dx2, colsum, accumulate, dres, out_dense; int nsplit;  // leod_linear_dgrad's extras: each bars the streaming kernels
+};
+// from the integers and flags of the C ABI (leod_linear_route has the same arguments): a16 / out16 = the entry's 16-bit option for the A rows
+// (dy_fmt, dy_bf16) / the stored rows (dx_fmt, out_bf16), ldo the stride of the stored rows
+enum : int { LF_LN = 1, LF_STATS = 2, LF_KSCALE = 4, LF_AUX = 8, LF_TOUT = 16, LF_DX2 = 32, LF_COLSUM = 64, LF_ACCUMULATE = 128, LF_DRES = 256 };
+static LinearProb linear_prob(int entry, int M, int N, int K, long lda, long ldo, int a16, int out16, int flags, int nsplit) {
+    const LinearEntryInfo& e = kLinearEntry[entry];
+    const bool h16 = leod_opfmt() == 2;             // forward launch of precision mode 16f: the 16-bit activations are fp16
+    LinearProb p{};
+    p.entry = entry; p.M = M; p.kc = e.dgrad ? N : K; p.nout = e.dgrad ? K : N;
+    p.lda = lda; p.a_dense = lda == p.kc; p.out_dense = ldo == p.nout;
+    p.a_fmt = entry == LE_LSRES_BF16 ? (h16 ? FMT_F16 : FMT_BF16) : entry == LE_LSRES_GELU16 ? FMT_F16PRE : a16 ? FMT_BF16 : FMT_F32;
+    p.out_fmt = entry == LE_LN_GELU16 ? FMT_F16PRE : entry == LE_LN_BF16 ? (h16 ? FMT_F16PRE : FMT_BF16) : out16 ? FMT_BF16 : FMT_F32;
+    p.ln = flags & LF_LN; p.stats = flags & LF_STATS; p.kscale = flags & LF_KSCALE; p.tout = flags & LF_TOUT;
+    p.act = (flags & LF_AUX) ? (e.dgrad ? ACT_MUL_GELU_GRAD : ACT_GELU_DUAL) : ACT_NONE;
+    p.aux_fmt = entry == LE_DGRAD_GELU16 ? FMT_F16PRE : FMT_F32;
+    p.dx2 = flags & LF_DX2; p.colsum = flags & LF_COLSUM; p.accumulate = flags & LF_ACCUMULATE; p.dres = flags & LF_DRES; p.nsplit = nsplit;
+    return p;
+}
+
+// The one routing function of the Linear forward / dgrad entries: the described problem -> the kernel that runs it, as a route code.
+// Row-streaming kernels first (stages 1-2), then the LDS-staged GEMMs (rows_gemm_kind, gemm16.hpp), then the register-direct one.  It
+// launches nothing and reads no device memory; the operand format (fp32 / bf16 / fp16) is the precision mode's and not part of the code:
+//   1000 + 100 KC + NTT    rowstream48_kernel<KC, NTT>: contraction 16 KC, slabs of NTT column tiles
+//   2000 + KC              rowstream_narrow_kernel<KC>: KC = 9 / 12 -> 48 columns, 18 / 24 -> 96 columns
+//   3000 + NTW             gemm_wide_bf16_kernel<NTW> (3 | 4)
+//   4000 + 100 NT + KCH    gemm_lds_kernel<NT, KCH> with the two-phase loader ALRowsM (KCH 48 | 64)
+//   5000 + 100 NT + KCH    gemm_lds_kernel<NT, KCH> with the plain loader ALRows
+//   6000 + 10 NT + KS      gemm16_kernel<NT, KS> (KS = 4: K split over the waves, else 1)
+//   < 0                    LEOD_ERR_*: what the entry returns
+enum : int { LR_RS48 = 1000, LR_NARROW = 2000, LR_WIDE = RG_WIDE, LR_LDS2P = RG_TWO_PHASE, LR_LDS = RG_PLAIN, LR_GEMM16 = 6000 };
+static int linear_route(const LinearProb& p) {
+    const LinearEntryInfo& e = kLinearEntry[p.entry];
+    const bool bf = leod_precision() == 1, a_bf16 = p.a_fmt == FMT_BF16;
+    const int M = p.M, kc = p.kc, nout = p.nout;
+    if ((kc & e.kc_mask) || (p.lda & e.lda_mask)) return LEOD_ERR_ARG;
+    if (e.needs16 && !bf) return e.needs16;
+    if (p.entry == LE_DGRAD_LNBWD) {                // the narrow kernel with the LayerNorm backward in its epilogue, or nothing
+        if (a_bf16 && use_rowstream_narrow96(M, kc, nout)) return LR_NARROW + kc / 16;
+        if (!use_rowstream_narrow(M, kc, nout)) return LEOD_ERR_UNSUPPORTED;
+        return (a_bf16 && !bf) ? LEOD_ERR_ARG : LR_NARROW + kc / 16;         // bf16 dy in mode f32: refused only after the narrow test
     }
-    if (aux_u) hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, false, false, 2>), grid, dim3(256), 0, s, dy, lddy, nullptr, kscale, nullptr, 0.f, W, nullptr, dx, aux, M, Nout);
-    else hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, false, false, 1>), grid, dim3(256), 0, s, dy, lddy, nullptr, kscale, nullptr, 0.f, W, nullptr, dx, aux, M, Nout);
+    const int nt = pick_nt(nout), nbn = cdiv(nout, 16 * nt);
+    const bool lds = use_gemm_lds(M, nbn) && (!p.ln || p.stats), out16 = p.out_fmt != FMT_F32;
+    const bool extras = p.dx2 || p.colsum || p.accumulate || p.dres || p.nsplit > 0;
+    if (p.entry == LE_DGRAD) {                      // dx_fmt = 1 runs on the LDS path or not at all
+        if (out16 && (!bf || extras || p.act || (nout & 3) || !lds)) return LEOD_ERR_UNSUPPORTED;
+        if (p.dres && (p.nsplit > 0 || p.accumulate)) return LEOD_ERR_ARG;
+    }
+    if (!a_bf16 && p.a_dense && p.out_dense && !extras && (!p.ln || p.stats) && !(p.entry == LE_DGRAD && out16)) {
+        if (e.narrow && !p.tout && !p.kscale && !p.act) {
+            if (e.narrow96 && kc == 384 && use_rowstream_narrow96(M, kc, nout)) return LR_NARROW + 24;
+            if (use_rowstream_narrow(M, kc, nout)) return LR_NARROW + kc / 16;
+        }
+        if (const int slab = (e.rs_pairs && (p.ln || !e.rs_ln_only)) ? rowstream_slab(M, nout, kc) : 0) {
+            if (e.rs_pairs & rs_bit(kc / 16, slab)) return LR_RS48 + 100 * (kc / 16) + slab;
+            if (e.rs_commits) return LEOD_ERR_UNSUPPORTED;
+        }
+    }
+    if (e.generic16 && ((kc | nout) & 3)) return LEOD_ERR_UNSUPPORTED;
+    if (lds) {
+        const int kind = rows_gemm_kind(M, kc, nout, nt, e.dgrad, e.lsres, p.a_fmt, p.ln, p.stats, p.kscale, p.act == ACT_MUL_GELU_GRAD);
+        return kind < RG_TWO_PHASE ? kind : kind + 100 * nt + gemm_lds_kch(kc);
+    }
+    return e.gemm16 ? LR_GEMM16 + 10 * nt + (gemm16_ksplit(M, kc, nbn) ? 4 : 1) : LEOD_ERR_UNSUPPORTED;
+}
+
+// the device pointers of a problem (what LinearProb only knows the presence of)
+struct LinearArgs {
+    const void* a; const float* ln_w; const float* ln_b; float eps; const float* kscale;    // A rows, LayerNorm on load, per-k scale
+    const float* W; const float* bias; const float* gamma; const float* res;                // EpLsRes: gamma, res (lnbwd: LayerNorm weight, dres)
+    void* out; long ldo; void* out2; long ld2;      // stored rows; second output: gelu(out) | t | dx2
+    float* stats; const void* aux;                  // (mean, rstd): written by a forward, read by lnbwd | pre-activation of ACT_MUL_GELU_GRAD
+    float* colsum; const float* dres;               // leod_linear_dgrad
+    const float* xin; float* dgamma; float* dbeta;  // leod_linear_dgrad_lnbwd
+};
+// ... and the switch that launches what linear_route decided.  E (LinearEntry) is a template argument so that a translation unit holds
+// the kernels of its own entries only.  Not a route: the launchers replace fp32 weights by their 16-bit shadow (bl_shadow_ptr) when the
+// weights lie in a registered buffer whose shadow is fresh -- a loader type picked from runtime state, same values, same kernel family.
+template <int E, int KC, int NTT>
+static int launch_rowstream48(const LinearProb& p, const LinearArgs& a, hipStream_t s) {
+    const dim3 grid = rowstream48_grid(KC, NTT, p.M, p.nout);
+    const float* x = reinterpret_cast<const float*>(a.a);
+    float* out = reinterpret_cast<float*>(a.out); float* out2 = reinterpret_cast<float*>(a.out2);
+    float* aux = reinterpret_cast<float*>(const_cast<void*>(a.aux));
+#define RS48(LNV, ACTV, DGV, BFV, UFV, OBV, ...) \
+    hipLaunchKernelGGL((rowstream48_kernel<KC, NTT, LNV, ACTV, DGV, BFV, UFV, OBV>), grid, dim3(256), 0, s, x, p.lda, __VA_ARGS__, p.M, p.nout)
+#define RS48_FWD(LNV, ACTV, BFV, UFV, OBV, ST, OUT, OUT2) RS48(LNV, ACTV, 0, BFV, UFV, OBV, ST, a.ln_w, a.ln_b, a.eps, a.W, a.bias, OUT, OUT2)
+#define RS48_DG(DGV, BFV, UFV, OBV) RS48(false, false, DGV, BFV, UFV, OBV, nullptr, a.kscale, nullptr, 0.f, a.W, nullptr, out, aux)
+    if constexpr (E == LE_LN_LINEAR) {              // the kernel derives (mean, rstd) itself and leaves them in stats
+        LEOD_BY_OPFMT({
+            if (p.ln && out2) RS48_FWD(true, true, OF, false, 0, a.stats, out, out2);
+            else if (p.ln) RS48_FWD(true, false, OF, false, 0, a.stats, out, nullptr);
+            else if (out2) RS48_FWD(false, true, OF, false, 0, nullptr, out, out2);
+            else RS48_FWD(false, false, OF, false, 0, nullptr, out, nullptr);
+        });
+    } else if constexpr (E == LE_LN_GELU16) { LEOD_BY_OPFMT16(RS48_FWD(true, true, OF, true, 0, a.stats, nullptr, out));
+    } else if constexpr (E == LE_LN_BF16) { LEOD_BY_OPFMT16(RS48_FWD(true, false, OF, false, OF, a.stats, out, nullptr));
+    } else if constexpr (E == LE_DGRAD) {
+        if (leod_precision() == 1) { if (aux) RS48_DG(2, 1, false, 0); else RS48_DG(1, 1, false, 0); }
+        else { if (aux) RS48_DG(2, 0, false, 0); else RS48_DG(1, 0, false, 0); }
+    } else if constexpr (E == LE_DGRAD_GELU16) {
+        if (p.out_fmt == FMT_BF16) RS48_DG(2, 1, true, 1); else RS48_DG(2, 1, true, 0);
+    }
+#undef RS48_DG
+#undef RS48_FWD
+#undef RS48
     return leod_launch_status();
+}
+template <int E, int KC>
+static int launch_rowstream_narrow(const LinearProb& p, const LinearArgs& a, hipStream_t s) {
+    constexpr int NTN = KC >= 18 ? 6 : 3;
+    const dim3 grid = rowstream_narrow_grid(p.M, NTN);
+#define NARROW(MODEV, BFV, AFV) hipLaunchKernelGGL((rowstream_narrow_kernel<KC, MODEV, BFV, AFV, NTN>), grid, dim3(NTN == 3 ? 256 : 512), 0, s, reinterpret_cast<const float*>(a.a), \
+                                                   a.W, a.bias, a.gamma, a.res, reinterpret_cast<float*>(a.out), p.M, a.xin, a.stats, a.dgamma, a.dbeta)
+    if constexpr (E == LE_LSRES) { LEOD_BY_OPFMT(NARROW(0, OF, 0)); }
+    else if constexpr (E == LE_LSRES_GELU16) { LEOD_BY_OPFMT16(NARROW(0, OF, 1)); }
+    else if constexpr (E == LE_DGRAD) { LEOD_BY_OPFMT_IF(false, NARROW(1, OF, 0)); }
+    else if constexpr (E == LE_DGRAD_LNBWD) {
+        if (p.a_fmt == FMT_BF16) NARROW(2, 1, 2);
+        else if constexpr (NTN == 3) { if (leod_precision() == 1) NARROW(2, 1, 0); else NARROW(2, 0, 0); }
+    }
+#undef NARROW
+    return leod_launch_status();
+}
+template <int E>
+static int launch_linear(int route, const LinearProb& p, const LinearArgs& a, hipStream_t s) {
+    if (route < 0) return route;
+    static constexpr LinearEntryInfo e = kLinearEntry[E];
+    const int par = route % 1000;
+    if (route < LR_NARROW) {
+#define RS_CASE(KCV, NTTV) if constexpr ((e.rs_pairs & rs_bit(KCV, NTTV)) != 0) { if (par == 100 * KCV + NTTV) return launch_rowstream48<E, KCV, NTTV>(p, a, s); }
+        RS_CASE(3, 9) RS_CASE(3, 12) RS_CASE(6, 9) RS_CASE(6, 8) RS_CASE(4, 12) RS_CASE(4, 8)
+#undef RS_CASE
+        return LEOD_ERR_ARG;
+    }
+    if (route < LR_WIDE) {
+        if constexpr (e.narrow) {
+            if (par == 9) return launch_rowstream_narrow<E, 9>(p, a, s);
+            if (par == 12) return launch_rowstream_narrow<E, 12>(p, a, s);
+        }
+        if constexpr (e.narrow96) {
+            if (par == 24) return launch_rowstream_narrow<E, 24>(p, a, s);
+            if constexpr (E == LE_DGRAD_LNBWD) { if (par == 18) return launch_rowstream_narrow<E, 18>(p, a, s); }
+        }
+        return LEOD_ERR_ARG;
+    }
+    if constexpr (E != LE_DGRAD_LNBWD) {
+        typedef typename std::conditional<e.dgrad, BLTrans, BLRows>::type BL;
+        const int M = p.M, kc = p.kc, nout = p.nout;
+        ALRows al{}; al.x = reinterpret_cast<const float*>(a.a); al.ld = p.lda; al.ln_w = a.ln_w; al.ln_b = a.ln_b; al.eps = a.eps;
+        al.kscale = a.kscale; al.stats_out = a.stats; al.K = kc; al.fmt = p.a_fmt;
+        auto launch = [&](const auto& ep) {
+            int rc = LEOD_OK;
+            if (route < LR_GEMM16) {                // LayerNorm on load: the LDS-staged kernels read (mean, rstd) that a launch of their own leaves in stats
+                if (p.ln) { rc = launch_row_stats(al.x, p.lda, a.stats, M, kc, a.eps, s); if (rc) return rc; al.stats_in = a.stats; }
+                const int kind = route < LR_LDS2P ? route : route / 1000 * 1000;
+                DISPATCH_NT(pick_nt(nout), { BL bl{a.W, (long)(e.dgrad ? nout : kc), nout, NT}; rc = launch_gemm_lds<NT>(kind, al, bl, ep, M, kc, cdiv(nout, 16 * NT), s); });
+            } else if constexpr (e.gemm16) {
+                DISPATCH_NT(pick_nt(nout), { BL bl{a.W, (long)(e.dgrad ? nout : kc), nout, NT}; rc = launch_gemm16<NT>(al, bl, ep, M, kc, cdiv(nout, 16 * NT), s); });
+            } else rc = LEOD_ERR_ARG;
+            return rc;
+        };
+        if constexpr (e.lsres) return launch(EpLsRes{reinterpret_cast<float*>(a.out), reinterpret_cast<float*>(a.out2), a.res, a.bias, a.gamma, (long)nout, nout});
+        else {
+            EpStore ep = ep_store(reinterpret_cast<float*>(a.out), a.ldo, nout);
+            ep.bias = a.bias; ep.out_fmt = p.out_fmt; ep.out2 = reinterpret_cast<float*>(a.out2); ep.ld2 = a.ld2; ep.nsplit = p.nsplit;
+            ep.act = p.act; ep.aux = reinterpret_cast<const float*>(a.aux); ep.ldaux = nout; ep.aux_fmt = p.aux_fmt;
+            ep.accumulate = p.accumulate; ep.colsum = a.colsum; ep.addsrc = a.dres;
+            return launch(ep);
+        }
+    }
+    return LEOD_ERR_ARG;
 }

@@ -514,6 +514,15 @@ def linear_wgrad_route(M, N, K, dy_fmt=0, x_fmt=0, K1=None, lddy=None, ldx=None,
                                             int(x_fmt == 1 if has_stats is None else has_stats), int(x2)))
 
 
+def linear_route(entry, M, N, K, lda=None, ldo=None, a16=0, out16=0, flags=0, nsplit=0) -> int:
+    """The kernel Linear forward / dgrad call number ``entry`` runs for this problem in the current precision mode, or the negative error
+    code it returns (``leod_linear_route`` in include/leod_hip.h lists the entries, the flags and the route codes; nothing is launched).
+    The strides default to dense rows."""
+    dgrad = entry >= 6
+    return int(_l().leod_linear_route(entry, M, N, K, (N if dgrad else K) if lda is None else lda, (K if dgrad else N) if ldo is None else ldo,
+                                      a16, out16, flags, nsplit))
+
+
 def linear_wgrad_group(problems) -> bool:
     """n <= 4 Linear weight gradients of one row count in ONE preparation / contraction / reduce launch (``leod_linear_wgrad_group``).
     problems: dicts with dy, x, dW, dbias and optionally stats + ln_w + ln_b (X = LayerNorm(x)) or gelu=True (x the fp16 pre-activation).
