@@ -369,6 +369,31 @@ int leod_pseudo_filter(const float* det, const int* det_cnt, float* lab, int* la
 int leod_adamw_clip_step(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                          float weight_decay, int step, float clip_value, float grad_scale, const float* hp_dev,
                          leod_stream_t stream);
+/* Per-segment statistics of an fp32 buffer g[n] in one segmented pass (two launches): for each of nseg segments (= the parameters of a
+ * flat gradient buffer) stats[s] = {sum |g|, sum g*g, max |g|} over its FINITE elements (double[nseg][3]), nonfinite[s] = its number of
+ * inf / NaN elements (classified by exponent bits), *total = their sum over all segments.  Elements outside every segment (the
+ * alignment padding between parameters) are never read into a result.  Sums are accumulated in double from the first add; there are no
+ * floating-point atomics, so results are bit-identical from run to run.  The reference computes grad.abs().mean() per parameter with one
+ * reduction and one read-back each (callbacks/utils/visualization.py:5-23) and GradScaler's inf check per tensor (train.py:243).
+ * Tables: seg [nseg][3] longs = {offset, length, index of the segment's first chunk}, once on the HOST (seg_host, validated on every call)
+ * and once on the device (seg_dev); chunk_dev [nchunk][2] ints = {segment, chunk index within the segment}, a segment of length L owning
+ * ceil(L / chunk_floats) consecutive chunks.  LEOD_ERR_ARG before any launch unless offsets are multiples of 4 floats, ascending and
+ * disjoint, lengths >= 1, every segment inside g[0, n), first-chunk indices running sums that end at nchunk, g 16-byte aligned and
+ * n < 2^31.  ws = caller-owned device scratch of the size leod_grad_stats_query reports.  nseg == 0: only *total = 0.
+ * leod_grad_stats_query (host only, no launch): *chunk_floats = floats per chunk, *ws_bytes = scratch bytes for nchunk chunks. */
+int leod_grad_stats_query(long nchunk, int* chunk_floats, long* ws_bytes);
+int leod_grad_stats(const float* g, long n, const long* seg_host, const long* seg_dev, int nseg, const int* chunk_dev, long nchunk,
+                    void* ws, double* stats, int* nonfinite, int* total, leod_stream_t stream);
+/* leod_adamw_clip_step that is NOT taken when a gradient is non-finite (what GradScaler.step does under the reference's precision 16,
+ * train.py:243), decided on the device: no host read-back.  nonfinite_total = the device total of leod_grad_stats over g; state =
+ * device int[2] {applied, skipped}; scratch = device float[8] owned by the caller (per-step scalars + skip word, written here).
+ * Launch one (one thread): total != 0 -> skip word set, ++skipped; else t = ++applied and {lr, 1-beta1^t, sqrt(1-beta2^t), grad_scale}
+ * (double pow rounded to float, as the entry above) go to scratch.  Launch two: the AdamW body of the entry above with those scalars;
+ * every thread returns at once on a skipped step, which leaves p, m, v AND g untouched, so moments and bias corrections do not advance.
+ * The host cannot know the outcome: registered weight shadows are marked stale either way. */
+int leod_adamw_clip_step_guarded(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float clip_value, float grad_scale, const int* nonfinite_total, int* state,
+                                 float* scratch, leod_stream_t stream);
 /* bf16 shadow of a flat fp32 parameter buffer (the reference keeps ONE copy of the weights and lets autocast convert them per op,
  * train.py:236-243 precision=16; here the Linear kernels of precision mode bf16 read a 16-bit copy made once per optimiser step).
  * leod_set_weight_shadow registers shadow16 (n bf16 values, caller-owned) for the n floats at base (shadow16 == NULL withdraws it);

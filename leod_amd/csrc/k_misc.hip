@@ -6,22 +6,54 @@
 
 // torch.optim.AdamW single-tensor update order: p *= 1 - lr*wd ; m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ;
 // denom = sqrt(v)/sqrt(bc2) + eps ; p -= (lr/bc1) * m / denom.  Gradients are clipped BY VALUE first.
+// One element of both entries below: the plain kernel and the guarded one run the same arithmetic.
+__device__ __forceinline__ void adamw_clip_elem(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long i,
+                                                float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt, float clip,
+                                                float grad_scale) {
+    float gi = g[i] * grad_scale;
+    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
+    float pi = p[i] * (1.f - lr * wd);
+    // exp_avg.lerp_(grad, 1 - beta1) ; exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    const float mi = m[i] + (gi - m[i]) * (1.f - beta1);
+    const float vi = v[i] * beta2 + (1.f - beta2) * (gi * gi);
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi = pi - (lr / bc1) * (mi / denom);
+    p[i] = pi; m[i] = mi; v[i] = vi; g[i] = gi;
+}
 __global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, long n, float lr, float beta1, float beta2,
                                                          float eps, float wd, float bc1, float bc2_sqrt, float clip,
                                                          float grad_scale, const float* __restrict__ hp) {
     if (hp) { lr = hp[0]; bc1 = hp[1]; bc2_sqrt = hp[2]; grad_scale = hp[3]; }   // per-step scalars from device memory (hipGraph replay)
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float gi = g[i] * grad_scale;
-        if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-        float pi = p[i] * (1.f - lr * wd);
-        // exp_avg.lerp_(grad, 1 - beta1) ; exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-        const float mi = m[i] + (gi - m[i]) * (1.f - beta1);
-        const float vi = v[i] * beta2 + (1.f - beta2) * (gi * gi);
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        pi = pi - (lr / bc1) * (mi / denom);
-        p[i] = pi; m[i] = mi; v[i] = vi; g[i] = gi;
-    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        adamw_clip_elem(p, g, m, v, i, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, clip, grad_scale);
+}
+
+// ---- the step that is not taken when a gradient is inf or NaN (the reference: GradScaler's check under precision 16, train.py:243) ----
+// `nonfinite_total` comes from leod_grad_stats over the same (already all-reduced) gradient buffer.  ONE thread decides: a non-zero total
+// sets the skip word and counts the step as skipped; otherwise the applied count advances to t and the per-step scalars of step t go to
+// device memory -- the formulas of leod_adamw_clip_step (double pow, rounded to float).  The counters are updated here and not in the
+// body, where a late workgroup would race the increment.  The body launch reads the skip word; every thread of a skipped step returns
+// before it touches p, m, v or g (the fmaxf / fminf clip would otherwise turn a NaN gradient into -clip and apply it).
+// scratch: device float[8], [0..3] = {lr, 1-beta1^t, sqrt(1-beta2^t), grad_scale}, [4] = the skip word (as an int).
+__global__ void adamw_decide_kernel(const int* __restrict__ nonfinite_total, int* __restrict__ state, float* __restrict__ scratch, float lr,
+                                    float beta1, float beta2, float grad_scale) {
+    int* skip = reinterpret_cast<int*>(scratch + 4);
+    if (*nonfinite_total != 0) { *skip = 1; state[1] += 1; return; }
+    const int t = state[0] + 1;
+    state[0] = t;
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+    const float bc2 = (float)(1.0 - pow((double)beta2, (double)t));
+    scratch[0] = lr; scratch[1] = bc1; scratch[2] = sqrtf(bc2); scratch[3] = grad_scale;
+    *skip = 0;
+}
+__global__ __launch_bounds__(256) void adamw_clip_guarded_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                                 float* __restrict__ v, long n, float beta1, float beta2, float eps, float wd,
+                                                                 float clip, const float* __restrict__ scratch) {
+    if (*reinterpret_cast<const int*>(scratch + 4) != 0) return;
+    const float lr = scratch[0], bc1 = scratch[1], bc2_sqrt = scratch[2], grad_scale = scratch[3];
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        adamw_clip_elem(p, g, m, v, i, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, clip, grad_scale);
 }
 
 static void shadow_mark_stale(const float* p, long n);
@@ -36,6 +68,21 @@ LEOD_API int leod_adamw_clip_step(float* p, float* g, float* m, float* v, long n
     hipLaunchKernelGGL(adamw_clip_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
                        bc1, sqrtf(bc2), clip_value, grad_scale, hp_dev);
     shadow_mark_stale(p, n);                          // bf16 shadows of these parameters (below) are out of date
+    return leod_launch_status();
+}
+LEOD_API int leod_adamw_clip_step_guarded(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                          float weight_decay, float clip_value, float grad_scale, const int* nonfinite_total, int* state,
+                                          float* scratch, hipStream_t stream) {
+    if (!p || !g || !m || !v || !nonfinite_total || !state || !scratch || n < 0) return LEOD_ERR_ARG;
+    hipLaunchKernelGGL(adamw_decide_kernel, dim3(1), dim3(1), 0, stream, nonfinite_total, state, scratch, lr, beta1, beta2, grad_scale);
+    if (leod_launch_status() != LEOD_OK) return LEOD_ERR_LAUNCH;
+    if (n == 0) return LEOD_OK;
+    const int grid = (int)min((long)2048, (n + 255) / 256);
+    hipLaunchKernelGGL(adamw_clip_guarded_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n, beta1, beta2, eps, weight_decay, clip_value,
+                       scratch);
+    // Whether the step was taken is known on the device only (no read-back here): the shadows are marked stale either way, and the refresh
+    // after a skipped step rewrites the values they already hold.
+    shadow_mark_stale(p, n);
     return leod_launch_status();
 }
 

@@ -446,7 +446,7 @@ class Module(_Base):
         from leod_amd.optim import FlatAdamW
         tc = self.full_config.training
         opt = FlatAdamW(self.mdl, lr=tc.learning_rate, weight_decay=tc.weight_decay,
-                        clip_value=tc.get('gradient_clip_val', None))
+                        clip_value=tc.get('gradient_clip_val', None), skip_nonfinite=tc.get('skip_nonfinite_steps', False))
         self._flat = opt.flat
         sp = tc.lr_scheduler
         if not sp.use:

@@ -1234,6 +1234,76 @@ def adamw_clip_step(p, g, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_d
                                      int(step), float(clip_value), float(grad_scale), _p(hp_dev), _stream()), 'adamw_clip_step')
 
 
+def adamw_clip_step_guarded(p, g, m, v, lr, nonfinite_total, state, scratch, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                            clip_value=0.0, grad_scale=1.0):
+    """``adamw_clip_step`` that is not taken when ``nonfinite_total`` (device int32[1], from ``grad_stats`` over ``g``) is non-zero: p, g, m, v
+    stay as they are and ``state`` (device int32[2] = applied, skipped) counts the step as skipped; otherwise the applied count advances and
+    gives the bias corrections.  ``scratch``: device float32[8] of the caller.  Decided on the device: no read-back."""
+    for t in (p, g, m, v):
+        _ck(t, name='adamw buffer')
+    _ck(nonfinite_total, torch.int32, 'nonfinite_total')
+    _ck(state, torch.int32, 'state')
+    _ck(scratch, name='scratch')
+    if nonfinite_total.numel() < 1 or state.numel() < 2 or scratch.numel() < 8:
+        raise ValueError('adamw_clip_step_guarded: nonfinite_total int32[1], state int32[2], scratch float32[8]')
+    check(_l().leod_adamw_clip_step_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay,
+                                             float(clip_value), float(grad_scale), _p(nonfinite_total), _p(state), _p(scratch), _stream()),
+          'adamw_clip_step_guarded')
+
+
+def _grad_stats_query(nchunk: int = 0):
+    cf, ws = (ctypes.c_int * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_grad_stats_query(int(nchunk), cf, ws), 'grad_stats_query')
+    return int(cf[0]), int(ws[0])
+
+
+def __getattr__(name):                                       # ops.GRAD_STATS_CHUNK: the library's own constant, asked once
+    if name == 'GRAD_STATS_CHUNK':
+        globals()[name] = _grad_stats_query()[0]
+        return globals()[name]
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
+def grad_stats_tables(offsets: Sequence[int], lengths: Sequence[int], chunk: Optional[int] = None):
+    """Host tables of ``grad_stats`` for segments (offset, length) in floats: seg int64 [nseg, 3] = (offset, length, first chunk) and
+    chunk int32 [nchunk, 2] = (segment, chunk index within the segment); a segment of length L owns ceil(L / chunk) consecutive chunks,
+    so no chunk straddles two segments.  Nothing is validated here: the library entry refuses a bad table."""
+    chunk = int(chunk if chunk is not None else __getattr__('GRAD_STATS_CHUNK'))
+    seg, cm = [], []
+    for s, (o, n) in enumerate(zip(offsets, lengths)):
+        seg.append((int(o), int(n), len(cm)))
+        cm.extend((s, k) for k in range(max(0, -(-int(n) // chunk))))
+    return (torch.tensor(seg, dtype=torch.int64).reshape(-1, 3), torch.tensor(cm, dtype=torch.int32).reshape(-1, 2))
+
+
+class GradStatsPlan:
+    """Everything ``grad_stats`` needs for one segment layout, made once: the tables on the host and on the device, the caller-owned
+    scratch and the outputs (``stats`` float64 [nseg, 3] = sum |g|, sum g^2, max |g| over finite elements; ``nonfinite`` int32 [nseg];
+    ``total`` int32 [1]) -- nothing is allocated during a step."""
+
+    def __init__(self, offsets: Sequence[int], lengths: Sequence[int], device):
+        self.seg_host, chunk_host = grad_stats_tables(offsets, lengths)
+        self.nseg, self.nchunk = int(self.seg_host.shape[0]), int(chunk_host.shape[0])
+        dev = torch.device(device)
+        self.seg_dev, self.chunk_dev = self.seg_host.to(dev), chunk_host.to(dev)
+        self.ws = torch.empty(max(1, _grad_stats_query(self.nchunk)[1] // 8), dtype=torch.float64, device=dev)
+        self.stats = torch.zeros((self.nseg, 3), dtype=torch.float64, device=dev)
+        self.nonfinite = torch.zeros((self.nseg,), dtype=torch.int32, device=dev)
+        self.total = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.lengths = torch.tensor([int(n) for n in lengths], dtype=torch.float64)
+
+
+def grad_stats(g: torch.Tensor, plan: GradStatsPlan):
+    """One segmented pass over the fp32 buffer ``g`` (two launches, no read-back) -> (plan.stats, plan.nonfinite, plan.total)."""
+    _ck(g, name='g')
+    for t, dt, n in ((plan.seg_dev, torch.int64, 'segment table'), (plan.chunk_dev, torch.int32, 'chunk table'), (plan.ws, torch.float64, 'workspace'),
+                     (plan.stats, torch.float64, 'stats'), (plan.nonfinite, torch.int32, 'nonfinite'), (plan.total, torch.int32, 'total')):
+        _ck(t, dt, n)
+    check(_l().leod_grad_stats(_p(g), g.numel(), _p(plan.seg_host), _p(plan.seg_dev), plan.nseg, _p(plan.chunk_dev), plan.nchunk,
+                                _p(plan.ws), _p(plan.stats), _p(plan.nonfinite), _p(plan.total), _stream()), 'grad_stats')
+    return plan.stats, plan.nonfinite, plan.total
+
+
 def rows_index_add(dst: torch.Tensor, src: torch.Tensor, idx: torch.Tensor) -> None:
     """dst[idx[j]] += src[j] on dim 0 (fp32, contiguous, UNIQUE int64 indices on the device): one launch, no atomics."""
     _ck(dst, name='dst')

@@ -91,6 +91,45 @@ class FlatParams:
         ops.PackCache.invalidate()                     # the kernel rewrote every parameter: packed weight copies are stale
         # (the library marked the bf16 shadow stale itself: leod_adamw_clip_step knows the buffer it rewrote)
 
+    # ---- per-parameter gradient statistics and the non-finite guard (csrc/k_gradstats.hip, leod_adamw_clip_step_guarded) ----------------
+    def _stats_plan(self) -> 'ops.GradStatsPlan':
+        """Segment table (one segment per parameter: its offset and ``numel()``; the alignment padding belongs to no segment), chunk map,
+        scratch and outputs of ``grad_stats``, built at the first use."""
+        if getattr(self, '_gs_plan', None) is None:
+            self._gs_plan = ops.GradStatsPlan(self.offsets, [p.numel() for p in self.params], self.grad.device)
+        return self._gs_plan
+
+    def grad_stats(self):
+        """One segmented pass over the gradient buffer as it stands (two launches, no read-back) -> device tensors (stats float64 [P, 3] =
+        sum |g|, sum g^2, max |g| over the finite elements of each parameter; nonfinite int32 [P]; total int32 [1]), P in ``self.params`` order.
+        The tensors are reused by the next call."""
+        return ops.grad_stats(self.grad, self._stats_plan())
+
+    def named_grad_stats(self, module: torch.nn.Module):
+        """``grad_stats`` zipped with the names of ``module``'s trainable parameters (the ``requires_grad`` order of ``self.params``):
+        -> [(name, stats[i], nonfinite[i])] of device tensors."""
+        names = [n for n, p in module.named_parameters() if p.requires_grad]
+        assert len(names) == len(self.params), 'module is not the one this FlatParams was built from'
+        stats, nonfinite, _ = self.grad_stats()
+        return [(n, stats[i], nonfinite[i]) for i, n in enumerate(names)]
+
+    def guard_state(self) -> torch.Tensor:
+        """Device int32[2] = (applied, skipped) steps of ``adamw_step_guarded``."""
+        if getattr(self, '_guard', None) is None:
+            self._guard = torch.tensor([self.step_count, 0], dtype=torch.int32, device=self.data.device)
+            self._guard_scratch = torch.zeros(8, dtype=torch.float32, device=self.data.device)
+        return self._guard
+
+    def adamw_step_guarded(self, lr, weight_decay=0.0, clip_value=1.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
+        """``adamw_step`` that is not taken when the gradient buffer holds an inf or a NaN (the reference: GradScaler under precision 16,
+        train.py:243): statistics pass, then the guarded entry, which decides on the device.  The applied-step count that gives the bias
+        corrections lives in ``guard_state()``; ``step_count`` is not advanced here (nothing is read back)."""
+        state = self.guard_state()
+        _, _, total = self.grad_stats()
+        ops.adamw_clip_step_guarded(self.data, self.grad, self.exp_avg, self.exp_avg_sq, lr, total, state, self._guard_scratch, betas=betas,
+                                    eps=eps, weight_decay=weight_decay, clip_value=clip_value, grad_scale=grad_scale)
+        ops.PackCache.invalidate()                     # taken or not is known on the device only: packed weight copies are dropped either way
+
     def touch(self):
         """Call after editing ``self.data`` (or any parameter through another alias than the parameter itself) outside the optimiser:
         cached derived copies of the weights (``ops.PackCache``, the bf16 shadow) are dropped."""

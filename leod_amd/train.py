@@ -104,11 +104,15 @@ def save_checkpoint(path: str, module, optimizer, scheduler, global_step: int, e
 def fit(config, module, data_module, max_steps: Optional[int] = None, val_check_interval: Optional[int] = None,
         log_every_n_steps: int = 100, ckpt_path: Optional[str] = None, resume_from: Optional[str] = None,
         on_step: Optional[Callable[[int, Dict[str, Any]], None]] = None, device: Optional[torch.device] = None, process_group=None,
-        limit_val_batches: Optional[int] = None) -> Dict[str, Any]:
+        limit_val_batches: Optional[int] = None, grad_flow_every: Optional[int] = None) -> Dict[str, Any]:
     """``pl.Trainer.fit`` of train.py:221-250 restated as a loop: ``fit_step`` (zero_grad, ``training_step``, backward, value clipping +
     AdamW, OneCycle) per batch until ``max_steps`` (default ``training.max_steps``) or ``training.max_epochs``; validation every
     ``val_check_interval`` steps (default ``validation.val_check_interval``) and at the end; a checkpoint at the end (and after every
-    validation) when ``ckpt_path`` is given.  -> {'global_step', 'epochs', 'loss' (per logged step), 'val' [(step, KPIs)], 'step_ms'}."""
+    validation) when ``ckpt_path`` is given.  -> {'global_step', 'epochs', 'loss' (per logged step), 'val' [(step, KPIs)], 'step_ms'}.
+    ``grad_flow_every``: rank 0 appends (step, ``FlatAdamW.grad_flow()``) -- the per-parameter mean |grad| chart of callbacks/gradflow.py --
+    to ``hist['grad_flow']`` every that many steps (one launch pair and one read-back each).  With ``training.skip_nonfinite_steps`` the
+    optimiser skips steps whose gradient holds an inf or a NaN (the scheduler advances all the same, as Lightning's does) and
+    ``hist['skipped_steps']`` is their number, read once at the end."""
     rank, world = _world(process_group)
     if device is None:
         device = next(module.parameters()).device
@@ -180,6 +184,8 @@ def fit(config, module, data_module, max_steps: Optional[int] = None, val_check_
             n_in_epoch += 1
             if on_step is not None:
                 on_step(step, out)
+            if grad_flow_every and rank == 0 and step % int(grad_flow_every) == 0:
+                hist.setdefault('grad_flow', []).append((step, opt.grad_flow()))
             if log_every_n_steps and step % log_every_n_steps == 0:
                 loss = float(out['loss'].detach())                   # the only read-back of the loop, once per logging interval
                 now = time.perf_counter()
@@ -203,4 +209,6 @@ def fit(config, module, data_module, max_steps: Optional[int] = None, val_check_
     if world > 1:
         dist.barrier(group=process_group)
     hist.update(global_step=step, epochs=epoch)
+    if getattr(opt, 'skip_nonfinite', False):
+        hist['skipped_steps'] = opt.skipped_steps
     return hist
