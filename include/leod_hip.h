@@ -244,7 +244,7 @@ int leod_conv_nhwc_wgrad(const float* dy, const float* x, float* dw, float* dbia
  * (device pointers / sizes per problem); wpack[k] / wpack_valid[k] as in leod_conv_nhwc_fwd.  forward: y_k = conv(x_k, w_k) with the
  * BatchNorm (sum, sumsq) of y_k into colstats[k] ([stat_rep[k]][2][Cout] doubles, zeroed; NULL: none).  dgrad: dx_k (+)= the input
  * gradient from dy_k [B,H,W,N]; problems of one call must write different dx buffers.  -3: not coverable, run the problems singly. */
-int leod_conv3x3_group_supported(int n, const int* H, const int* W, int Cin, int Cout);   /* 1: the forward call covers these maps (dgrad: ask with (Cout, Cin)) */
+int leod_conv3x3_group_supported(int n, const int* H, const int* W, int Cin, int Cout);   /* 1: n in 1..8 and every map routes to 110 (leod_conv_route): the forward call covers them (dgrad: ask with (Cout, Cin)) */
 int leod_conv3x3_group_fwd(int n, const float* const* x, const float* const* w, float* const* y, double* const* colstats,
                            const int* stat_rep, void* const* wpack, const int* wpack_valid, const int* B, const int* H, const int* W,
                            int Cin, int Cout, leod_stream_t stream);
@@ -256,6 +256,33 @@ int leod_conv3x3_group_dgrad(int n, const float* const* dy, const float* const* 
 long leod_conv3x3_group_wgrad_workspace_floats(int B, int H, int W, int Cin, int N);
 int leod_conv3x3_group_wgrad(int n, const float* const* dy, const float* const* x, float* const* dw, float* const* ws, const int* B,
                              const int* H, const int* W, int Cin, int N, leod_stream_t stream);
+
+/* Which kernel a dense-convolution call runs for this problem in the current precision mode, or the negative error it returns (NULL pointers
+ * apart) -- a query: nothing is launched, no memory is read.  The calls themselves switch on the same value, so the two cannot differ.
+ * entry: 0 leod_conv_nhwc_fwd, 1 leod_conv_nhwc_dgrad, 2 leod_conv_nhwc_wgrad, 3 leod_stem_conv_fwd, 4 leod_stem_conv_wgrad.  B, H, W, Cin,
+ * N, ks, stride, pad as that call takes them (H, W: the conv's input map; the stem's stored frame).  Hp, Wp: the padded frame of the stem
+ * entries (0: H, W); ignored by the others.  flags, what the call is given: 1 bias, 2 colstats, 4 bn_w (eval BatchNorm), 8 wpack, 16 ws,
+ * 32 dbias, 64 accumulate, 128 x_is_u8, 256 the address of x is a multiple of 4 (stem).  A code is read together with the entry:
+ *   110 / 120              direct 3x3 from the LDS halo, stride 1 / 2 (forward; 110 also the stride-1 dgrad); reads the 16-bit per-tap pack in wpack
+ *   220                    direct stride-2 3x3 dgrad; reads the bf16 per-tap pack in wpack
+ *   300 + c                1x1 weight gradient on the wgradw kernel, configuration c   (the codes of leod_linear_wgrad_route)
+ *   400 + 10 TN + 4        1x1 weight gradient on the wgrad16 kernel, TN x 4 blocks of 16 columns
+ *   500                    direct 3x3 weight gradient into the workspace ws + reduce
+ *   600 + NT / 610 + NT    stem forward on the bf16 patch (NT = N / 16: 2, 3) / on the uint8 patch (NT 1..4)
+ *   620 + NT / 630 + NT    stem weight gradient on the bf16 patch (NT 1..4; 4 runs as two slices of 32 channels) / on the uint8 patch
+ *   700 / 800 / 900 + 10 TN + 4   wgrad16 kernel on the im2col loader of an NHWC map / the stem's uint8 frame / the stem's fp32 frame
+ *   1x1 forward and dgrad run as Linear layers over the pixel rows, with the codes of leod_linear_route, except that the wide-tile code
+ *   carries one more digit (3043 here is 3003 there):
+ *   3000 + 10 NT + NTW     persistent wide-tile kernel, workgroups of 64 NTW columns (NT: column tiling of its weight loader)
+ *   4000 / 5000 + 100 NT + KCH    LDS-staged kernel, NT blocks of 16 columns, K chunks of KCH, two-phase / plain row loader
+ *   6000 + 10 NT + KS      register-direct kernel, K split over KS waves (1, 4)
+ *   implicit GEMMs of ks > 1 and of the stem's generic path, 10000 L + form: L = 1 im2col of an NHWC map, 2 parity classes of a stride-2
+ *   3x3 dgrad ("live taps"), 3 / 4 im2col of the stem's uint8 / fp32 frame;
+ *   L7000 + 100 NT + KCH   LDS-staged kernel on the K-contiguous fp32 copy of the weights in wpack (the only GEMM form that reads wpack)
+ *   L8000 + 100 NT + KCH   LDS-staged kernel on the weights in their native layout
+ *   L9000 + 10 NT + KS     register-direct kernel on the weights in their native layout
+ *   0                      no output rows: nothing to do;    -1 / -3: what the call returns for these arguments */
+int leod_conv_route(int entry, int B, int H, int W, int Cin, int N, int ks, int stride, int pad, int flags, int Hp, int Wp);
 
 /* Depthwise convolution (groups == channels) on NHWC maps, w[C,1,ks,ks]: the depthwise half of DWConv (network_blocks.py:57-76, selected
  * by `depthwise` at yolo_pafpn.py:37 / yolo_head.py:52) and conv3x3_dws of the ConvLSTM (models/layers/rnn.py:20-30,50-55).  Same epilogue

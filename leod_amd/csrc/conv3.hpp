@@ -10,7 +10,6 @@ int conv3s1_launch(const float* x, const float* w, float* y, double* colstats, i
                    const float* bn_w = nullptr, const float* bn_b = nullptr, const float* bn_rm = nullptr, const float* bn_rv = nullptr,
                    float bn_eps = 1e-5f);      // bn_w != NULL: eval-mode BatchNorm + SiLU applied to the finished rows (forward only)
 // n <= 8 independent stride-1 problems of one (Cin, Cout) geometry in one launch (forward with statistics, or transposed = 1: input gradients)
-bool conv3s1_group_supported(int n, const int* H, const int* W, int Cin, int Cout);
 int conv3s1_group(int n, const float* const* x, const float* const* w, float* const* y, double* const* colstats, const int* stat_rep,
                   const int* accumulate, const int* B, const int* H, const int* W, int Cin, int Cout, int transposed, void* const* wpack,
                   const int* packed, hipStream_t stream);

@@ -959,6 +959,24 @@ __global__ __launch_bounds__(256) void gemm16_kernel(AL al, BL bl, EP ep, int M,
     ep.template run<NT, BL>(acc, bl, row0, nblk, lane, M);
 }
 
+// column tiles (of 16) per workgroup of the row GEMMs: the NT in 1..4 that pads N the least (the widest on a tie)
+static inline int pick_nt(int N) {
+    int best = 1; long bestpad = 1L << 60;
+    for (int nt = 4; nt >= 1; --nt) {
+        const long pad = (long)cdiv(N, 16 * nt) * 16 * nt;
+        if (pad < bestpad) { bestpad = pad; best = nt; }
+    }
+    return best;
+}
+
+#define DISPATCH_NT(NTV, ...)                                          \
+    switch (NTV) {                                                     \
+        case 1: { constexpr int NT = 1; __VA_ARGS__; } break;          \
+        case 2: { constexpr int NT = 2; __VA_ARGS__; } break;          \
+        case 3: { constexpr int NT = 3; __VA_ARGS__; } break;          \
+        default: { constexpr int NT = 4; __VA_ARGS__; } break;         \
+    }
+
 // fewer than ~2 workgroups per CU and a long K loop: split K across the 4 waves of each workgroup
 static inline bool gemm16_ksplit(int M, int K, int nblocks_n) { return (long)cdiv(M, 64) * nblocks_n < 512 && K >= 128; }
 template <int NT, class AL, class BL, class EP>

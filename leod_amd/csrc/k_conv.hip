@@ -7,25 +7,7 @@
 //   * their dgrad / wgrad.
 // Epilogues: raw store (+bias), raw store + per-channel (sum, sumsq) for training BatchNorm,
 // or folded eval-BatchNorm + SiLU.
-#include "gemm16.hpp"
-#include "conv3.hpp"
-#include "stem.hpp"
-
-static inline int pick_nt(int N) {
-    int best = 1; long bestpad = 1L << 60;
-    for (int nt = 4; nt >= 1; --nt) {
-        const long pad = (long)cdiv(N, 16 * nt) * 16 * nt;
-        if (pad < bestpad) { bestpad = pad; best = nt; }
-    }
-    return best;
-}
-#define DISPATCH_NT(NTV, ...)                                          \
-    switch (NTV) {                                                     \
-        case 1: { constexpr int NT = 1; __VA_ARGS__; } break;          \
-        case 2: { constexpr int NT = 2; __VA_ARGS__; } break;          \
-        case 3: { constexpr int NT = 3; __VA_ARGS__; } break;          \
-        default: { constexpr int NT = 4; __VA_ARGS__; } break;         \
-    }
+#include "conv_route.hpp"
 
 static EpStore conv_epilogue(float* out, int N, const float* bias, double* colstats, int stat_rep, const float* bn_w, const float* bn_b,
                              const float* bn_rm, const float* bn_rv, float bn_eps) {
@@ -50,50 +32,6 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* __restrict_
 static inline void launch_conv_pack(const float* w, float* out, int N, int Cin, int KK, int mode, hipStream_t s) {
     const long total = (long)N * Cin * KK;
     hipLaunchKernelGGL(conv_pack_kernel, dim3((int)min((long)1024, (total + 255) / 256)), dim3(256), 0, s, w, out, N, Cin, KK, mode);
-}
-
-// y[B,Ho,Wo,N] = conv(x[B,H,W,Cin] NHWC, w[N,Cin,ks,ks]) (+bias) ; Ho = (H + 2*pad - ks)/stride + 1
-//   colstats != NULL : also accumulate per-channel (sum, sumsq) in double for training BatchNorm, spread over stat_rep
-//                      replicas [stat_rep][2][N] (power of two, zero-initialised by the caller; leod_bn_silu_fwd folds them)
-//   bn_w != NULL     : eval mode, y = silu(bn(conv)) with running statistics folded in
-LEOD_API int leod_conv_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, double* colstats, int stat_rep,
-                                const float* bn_w, const float* bn_b, const float* bn_rm, const float* bn_rv, float bn_eps,
-                                int B, int H, int W, int Cin, int N, int ks, int stride, int pad, float* wpack, int wpack_valid,
-                                hipStream_t stream) {
-    LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
-    if (!x || !w || !y || (Cin & 3) || (stat_rep > 1 && (stat_rep & (stat_rep - 1)))) return LEOD_ERR_ARG;
-    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    const int M = B * Ho * Wo, K = ks * ks * Cin;
-    // PAFPN / head 3x3 convs in precision mode bf16: direct convolution from an LDS-resident input halo (k_conv3.hip)
-    // (eval mode, bn_w != NULL: the folded BatchNorm + SiLU run in the direct kernel's row epilogue -- the pseudo-label pass spent a third
-    // of its device time in the implicit-GEMM form of these convs)
-    if (ks == 3 && stride == 1 && pad == 1 && !bias && !(bn_w && colstats) && wpack && conv3s1_supported(H, W, Cin, N))
-        return conv3s1_launch(x, w, y, colstats, stat_rep, 0, B, H, W, Cin, N, 0, wpack, stream, 1, wpack_valid, bn_w, bn_b, bn_rm, bn_rv, bn_eps);
-    if (ks == 3 && stride == 2 && pad == 1 && !bias && !(bn_w && colstats) && wpack && conv3s2_fwd_supported(B, H, W, Cin, N))
-        return conv3s1_launch(x, w, y, colstats, stat_rep, 0, B, H, W, Cin, N, 0, wpack, stream, 2, wpack_valid, bn_w, bn_b, bn_rm, bn_rv, bn_eps);
-    EpStore ep = conv_epilogue(y, N, bias, colstats, stat_rep, bn_w, bn_b, bn_rm, bn_rv, bn_eps);
-    const int nt = pick_nt(N);
-    int rc = LEOD_OK;
-    const bool lds = use_gemm_lds(M, cdiv(N, 16 * nt));      // large M: coalesced LDS-staged operands
-    if (ks == 1 && stride == 1 && pad == 0) {
-        ALRows al{}; al.x = x; al.ld = Cin; al.K = Cin;
-        DISPATCH_NT(nt, { BLRows bl{w, (long)Cin, N, NT};
-                          rc = lds ? launch_gemm_lds<NT>(rows_gemm_kind(al, bl, ep, M, K, NT), al, bl, ep, M, K, cdiv(N, 16 * NT), stream)
-                                   : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-    } else {
-        ALConvNHWC al{x, H, W, Cin, Ho, Wo, ks, stride, pad};
-        if (wpack && lds) {
-            // scratch given: repack the weights K-contiguous first (N*Cin*ks*ks floats, a few microseconds), then the B
-            // operand is a plain row-major matrix like a Linear weight
-            if (!wpack_valid) launch_conv_pack(w, wpack, N, Cin, ks * ks, 0, stream);
-            DISPATCH_NT(nt, { BLRows bl{wpack, (long)K, N, NT}; rc = launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-            return rc;
-        }
-        DISPATCH_NT(nt, { BLConvW bl{w, N, Cin, ks * ks, NT};
-                          rc = lds ? launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream)
-                                   : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-    }
-    return rc;
 }
 
 // =====================================================================================================================
@@ -250,132 +188,6 @@ static int launch_stem_u8(const uint8_t* x, const float* w, float* y, int B, int
     return leod_launch_status();
 }
 
-// Stem: y[B,Ho,Wo,N] = conv(pad(x[B,Cin,H,W] NCHW) , w[N,Cin,ks,ks]) with Hp,Wp the padded size
-// (Ho = (Hp + 2*pad - ks)/stride + 1).  x_is_u8: raw uint8 stacked-histogram voxels.
-LEOD_API int leod_stem_conv_fwd(const void* x, int x_is_u8, const float* w, float* y, int B, int Cin, int H, int W,
-                                int Hp, int Wp, int N, int ks, int stride, int pad, hipStream_t stream) {
-    LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
-    if (!x || !w || !y || ((Cin * ks * ks) & 3)) return LEOD_ERR_ARG;
-    if (ks < 1 || ks > 15) return LEOD_ERR_UNSUPPORTED;
-    const int Ho = (Hp + 2 * pad - ks) / stride + 1, Wo = (Wp + 2 * pad - ks) / stride + 1;
-    const int M = B * Ho * Wo, K = Cin * ks * ks;
-    EpStore ep = conv_epilogue(y, N, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f);
-    const int nt = pick_nt(N);
-    int rc = LEOD_OK;
-    const bool lds = use_gemm_lds(M, cdiv(N, 16 * nt));
-    static const int stem_patch = 1;
-    if (stem_patch && ks == 7 && x_is_u8 && leod_precision() == 1 && stem_fwd_bf16_supported(x, Cin, H, W, N, stride, pad))
-        return stem_fwd_bf16_launch(x, w, y, B, Cin, H, W, Ho, Wo, N, stream);         // k_stem.hip: bf16 patch, weights resident in LDS
-    if (stem_patch && ks == 7 && x_is_u8 && stride == 4 && pad == 3 && N <= 64 && !(N & 15) && !(W & 3) && Cin * 19 * 72 <= 60000 &&
-        ((uintptr_t)x & 3) == 0 && ((long)Cin * H * W) % 4 == 0) {
-        // LDS-resident uint8 patch kernel (dedicated to the RVT stem geometry); anything else takes the generic path
-        switch (N / 16) {
-            case 1: return launch_stem_u8<1>((const uint8_t*)x, w, y, B, Cin, H, W, Ho, Wo, N, stream);
-            case 2: return launch_stem_u8<2>((const uint8_t*)x, w, y, B, Cin, H, W, Ho, Wo, N, stream);
-            case 3: return launch_stem_u8<3>((const uint8_t*)x, w, y, B, Cin, H, W, Ho, Wo, N, stream);
-            default: return launch_stem_u8<4>((const uint8_t*)x, w, y, B, Cin, H, W, Ho, Wo, N, stream);
-        }
-    }
-    if (x_is_u8) {
-        ALStemNCHW<uint8_t> al{(const uint8_t*)x, Cin, H, W, Ho, Wo, ks, stride, pad};
-        DISPATCH_NT(nt, { BLRows bl{w, (long)K, N, NT};
-                          rc = lds ? launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream)
-                                   : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-    } else {
-        ALStemNCHW<float> al{(const float*)x, Cin, H, W, Ho, Wo, ks, stride, pad};
-        DISPATCH_NT(nt, { BLRows bl{w, (long)K, N, NT};
-                          rc = lds ? launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream)
-                                   : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(N, 16 * NT), stream); });
-    }
-    return rc;
-}
-
-// dx[B,H,W,Cin] (=|+=) conv_transpose(dy[B,Ho,Wo,N], w)
-LEOD_API int leod_conv_nhwc_dgrad(const float* dy, const float* w, float* dx, int accumulate, int B, int H, int W, int Cin,
-                                  int N, int ks, int stride, int pad, float* wpack, int wpack_valid, hipStream_t stream) {
-    if (!dy || !w || !dx || (N & 3)) return LEOD_ERR_ARG;
-    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    const int M = B * H * W, K = ks * ks * N;
-    if (ks == 3 && stride == 1 && pad == 1 && wpack && conv3s1_supported(H, W, N, Cin))
-        return conv3s1_launch(dy, w, dx, nullptr, 0, accumulate, B, H, W, N, Cin, 1, wpack, stream, 1, wpack_valid);
-    if (ks == 3 && stride == 2 && pad == 1 && wpack && conv3s2_dgrad_supported(H, W, Cin, N))
-        return conv3s2_dgrad_launch(dy, w, dx, accumulate, B, H, W, Cin, N, wpack, stream, wpack_valid);
-    EpStore ep{}; ep.out = dx; ep.ld = Cin; ep.N = Cin; ep.accumulate = accumulate;
-    const int nt = pick_nt(Cin);
-    int rc = LEOD_OK;
-    const int Q = B * (H / 2) * (W / 2);
-    if (ks == 3 && stride == 2 && pad == 1 && !(H & 1) && !(W & 1) && Q % 16 == 0) {
-        // live-tap formulation: rows grouped by input parity class, 2.25 taps per pixel on average instead of 9
-        ALConvT2 al{dy, H, W, Ho, Wo, N, Q};
-        ep.rm_Q = Q; ep.rm_H = H; ep.rm_W = W;
-        const bool lds2 = use_gemm_lds(M, cdiv(Cin, 16 * nt)) && Q % 128 == 0;    // a (64|128)-row workgroup must not mix classes
-        if (wpack && lds2) {
-            if (!wpack_valid) launch_conv_pack(w, wpack, N, Cin, 9, 1, stream);
-            DISPATCH_NT(nt, { BLPackT2 bl{wpack, N, Cin, NT}; rc = launch_gemm_lds<NT>(al, bl, ep, M, 4 * N, cdiv(Cin, 16 * NT), stream); });
-            return rc;
-        }
-        DISPATCH_NT(nt, { BLConvWT2 bl{w, N, Cin, NT};
-                          rc = lds2 ? launch_gemm_lds<NT>(al, bl, ep, M, 4 * N, cdiv(Cin, 16 * NT), stream)
-                                    : launch_gemm16<NT>(al, bl, ep, M, 4 * N, cdiv(Cin, 16 * NT), stream); });
-        return rc;
-    }
-    const bool lds = use_gemm_lds(M, cdiv(Cin, 16 * nt));
-    if (ks == 1 && stride == 1 && pad == 0) {
-        ALRows al{}; al.x = dy; al.ld = N; al.K = N;
-        DISPATCH_NT(nt, { BLTrans bl{w, (long)Cin, Cin, NT};
-                          rc = lds ? launch_gemm_lds<NT>(rows_gemm_kind(al, bl, ep, M, K, NT), al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream)
-                                   : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream); });
-    } else {
-        ALConvT al{dy, H, W, Ho, Wo, N, ks, stride, pad};
-        if (wpack && lds) {
-            if (!wpack_valid) launch_conv_pack(w, wpack, N, Cin, ks * ks, 1, stream);         // wd[c][tap*N + n]: B(col = c, k' = tap*N + n)
-            DISPATCH_NT(nt, { BLRows bl{wpack, (long)K, Cin, NT}; rc = launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream); });
-            return rc;
-        }
-        DISPATCH_NT(nt, { BLConvWT bl{w, N, Cin, ks * ks, NT};
-                          rc = lds ? launch_gemm_lds<NT>(al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream)
-                                   : launch_gemm16<NT>(al, bl, ep, M, K, cdiv(Cin, 16 * NT), stream); });
-    }
-    return rc;
-}
-
-template <class XL>
-static int wgrad_any(const float* dy, const XL& xl, float* dW, long ldw, float* dbias, int M, int N, int K, hipStream_t s) {
-    static const int conv_w = 0;
-    if (conv_w && use_wgradw(M)) return launch_wgradw(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
-    if (N % 48 == 0) return launch_wgrad16<3, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
-    if (N % 64 == 0) return launch_wgrad16<4, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
-    if (N % 32 == 0) return launch_wgrad16<2, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
-    return launch_wgrad16<1, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
-}
-
-// dw[N,Cin,ks,ks] += dy^T im2col(x) ; dbias[N] += colsum(dy)
-// floats of workspace leod_conv_nhwc_wgrad wants for this shape in the current precision mode (0: none)
-LEOD_API long leod_conv_nhwc_wgrad_workspace_floats(int B, int H, int W, int Cin, int N, int ks, int stride, int pad, int has_bias) {
-    if (ks == 3 && pad == 1 && !has_bias && conv3_wgrad_supported(H, W, Cin, N, stride))
-        return (long)conv3_wgrad_workspace_floats(B, H, W, Cin, N, stride);
-    return 0;
-}
-
-LEOD_API int leod_conv_nhwc_wgrad(const float* dy, const float* x, float* dw, float* dbias, float* ws, int B, int H, int W, int Cin,
-                                  int N, int ks, int stride, int pad, hipStream_t stream) {
-    if (!dy || !x || !dw) return LEOD_ERR_ARG;
-    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    const int M = B * Ho * Wo, K = ks * ks * Cin;
-    if (ks == 1 && stride == 1 && pad == 0) {
-        XRows xl{x, (long)Cin, nullptr, nullptr, nullptr, nullptr, 0, 0};
-        // 1 x 1 convs are Linear layers over the pixel rows: the wave-tiled weight gradient of the Linear layers for the large maps in
-        // bf16 mode (22 -> 15, 28 -> 23, 18 -> 12 us on the PAFPN shapes; fp32 mode: 24 -> 28, 22 -> 26 us, not used)
-        static const int w11 = 1;
-        if (w11 && leod_precision() == 1 && use_wgradw(M)) return launch_wgradw(dy, (long)N, xl, dw, (long)Cin, dbias, M, N, K, stream);
-        return wgrad_any(dy, xl, dw, (long)Cin, dbias, M, N, K, stream);
-    }
-    if (ks == 3 && pad == 1 && !dbias && ws && conv3_wgrad_supported(H, W, Cin, N, stride))
-        return conv3_wgrad_launch(dy, x, dw, ws, B, H, W, Cin, N, stride, stream);
-    XConvNHWC xl{x, H, W, Cin, Ho, Wo, ks, stride, pad};
-    return wgrad_any(dy, xl, dw, (long)K, dbias, M, N, K, stream);
-}
-
 // =====================================================================================================================
 // Dedicated stem weight gradient for uint8 voxels: dW[n][k] += sum_pixels dY[pixel][n] * im2col(x)[pixel][k].
 // Same LDS-resident patch as stem_u8_fwd_kernel.  A workgroup walks over 4 x 16-pixel tiles (grid-stride), owns one
@@ -526,21 +338,204 @@ static int launch_stem_u8_wgrad(const float* dy, const uint8_t* x, float* dW, in
     return leod_launch_status();
 }
 
+// =====================================================================================================================
+// The launch switch: what conv_route (conv_route.hpp) decided, launched.  E (ConvEntry) is a template argument so that an entry point holds
+// the kernels of its own routes only.
+// =====================================================================================================================
+// the device pointers of a problem (what ConvProb only knows the presence of).  in / out: x -> y (forward), dy -> dx (dgrad); the weight
+// gradients read dy and in (= x) and add to dw
+struct ConvArgs {
+    const void* in; const float* w; const float* bias; float* out;
+    double* colstats; int stat_rep; const float* bn_w; const float* bn_b; const float* bn_rm; const float* bn_rv; float bn_eps;
+    float* wpack; int wpack_valid;
+    const float* dy; float* dw; float* dbias; float* ws;
+};
+// the GEMM forms of a route code (conv_route.hpp): LDS-staged (7000 / 8000 + 100 NT + KCH) or, REG, register-direct (9000 + 10 NT + KS);
+// bl(NT): the weight loader for that column tiling
+template <bool REG, class AL, class MakeBL>
+static int launch_conv_gemm(int route, const AL& al, MakeBL bl, const EpStore& ep, int M, int K, int nout, hipStream_t s) {
+    const int form = route % CR_LOADER / 1000 * 1000, par = route % 1000;
+    int rc = LEOD_ERR_ARG;
+    if (form != CR_REG_NATIVE) { DISPATCH_NT(par / 100, rc = launch_gemm_lds<NT>(al, bl(NT), ep, M, K, cdiv(nout, 16 * NT), s)); }
+    else if constexpr (REG) { DISPATCH_NT(par / 10, rc = launch_gemm16<NT>(al, bl(NT), ep, M, K, cdiv(nout, 16 * NT), s)); }
+    return rc;
+}
+// 1x1: the Linear kernels on the pixel rows (3000 + 10 NT + NTW | 4000 / 5000 + 100 NT + KCH | 6000 + 10 NT + KS)
+template <class BL>
+static int launch_conv_rows(int route, const float* x, const float* w, long ldw, const EpStore& ep, int M, int K, int nout, hipStream_t s) {
+    ALRows al{}; al.x = x; al.ld = K; al.K = K;
+    const int par = route % 1000;
+    int rc = LEOD_ERR_ARG;
+    if (route >= CR_GEMM16) { DISPATCH_NT(par / 10, { BL bl{w, ldw, nout, NT}; rc = launch_gemm16<NT>(al, bl, ep, M, K, cdiv(nout, 16 * NT), s); }); }
+    else if (route < RG_TWO_PHASE) { DISPATCH_NT(par / 10, { BL bl{w, ldw, nout, NT}; rc = launch_gemm_lds<NT>(RG_WIDE + par % 10, al, bl, ep, M, K, cdiv(nout, 16 * NT), s); }); }
+    else { DISPATCH_NT(par / 100, { BL bl{w, ldw, nout, NT}; rc = launch_gemm_lds<NT>(route / 1000 * 1000, al, bl, ep, M, K, cdiv(nout, 16 * NT), s); }); }
+    return rc;
+}
+// base + 10 TN + 4: wgrad16_kernel<TN, 4> on the X loader of the entry
+template <class XL>
+static int launch_conv_wgrad16(int route, const float* dy, const XL& xl, float* dW, long ldw, float* dbias, int M, int N, int K, hipStream_t s) {
+    switch (route % 100 / 10) {
+        case 3: return launch_wgrad16<3, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
+        case 4: return launch_wgrad16<4, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
+        case 2: return launch_wgrad16<2, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
+        case 1: return launch_wgrad16<1, 4>(dy, (long)N, xl, dW, ldw, dbias, M, N, K, s);
+    }
+    return LEOD_ERR_ARG;
+}
+#define STEM_NT(CALL) switch (route % 10) { case 1: { constexpr int NT = 1; return CALL; } case 2: { constexpr int NT = 2; return CALL; } \
+                                            case 3: { constexpr int NT = 3; return CALL; } case 4: { constexpr int NT = 4; return CALL; } } return LEOD_ERR_ARG
+template <int E>
+static int launch_conv(int route, const ConvProb& p, const ConvArgs& a, hipStream_t s) {
+    if (route <= 0) return route;                   // the entry's error, or nothing to do
+    const int B = p.B, H = p.H, W = p.W, Cin = p.Cin, N = p.N, ks = p.ks, stride = p.stride, pad = p.pad;
+    const int Ho = p.Ho(), Wo = p.Wo(), M = p.M(), K = p.K(), L = route / CR_LOADER;
+    const bool packed = route % CR_LOADER / 1000 * 1000 == CR_LDS_PACKED;
+    if constexpr (E == CE_FWD) {
+        const float* x = reinterpret_cast<const float*>(a.in);
+        if (route == CR_DIRECT3 + 10 || route == CR_DIRECT3 + 20)
+            return conv3s1_launch(x, a.w, a.out, a.colstats, a.stat_rep, 0, B, H, W, Cin, N, 0, a.wpack, s, route == CR_DIRECT3 + 10 ? 1 : 2, a.wpack_valid,
+                                  a.bn_w, a.bn_b, a.bn_rm, a.bn_rv, a.bn_eps);
+        const EpStore ep = conv_epilogue(a.out, N, a.bias, a.colstats, a.stat_rep, a.bn_w, a.bn_b, a.bn_rm, a.bn_rv, a.bn_eps);
+        if (L == 0) return launch_conv_rows<BLRows>(route, x, a.w, (long)Cin, ep, M, K, N, s);
+        const ALConvNHWC al{x, H, W, Cin, Ho, Wo, ks, stride, pad};
+        if (packed) {
+            if (!a.wpack_valid) launch_conv_pack(a.w, a.wpack, N, Cin, ks * ks, 0, s);
+            return launch_conv_gemm<false>(route, al, [&](int nt) { return BLRows{a.wpack, (long)K, N, nt}; }, ep, M, K, N, s);
+        }
+        return launch_conv_gemm<true>(route, al, [&](int nt) { return BLConvW{a.w, N, Cin, ks * ks, nt}; }, ep, M, K, N, s);
+    } else if constexpr (E == CE_DGRAD) {
+        const float* dy = reinterpret_cast<const float*>(a.in);
+        const int acc = p.accumulate ? 1 : 0;
+        if (route == CR_DIRECT3 + 10) return conv3s1_launch(dy, a.w, a.out, nullptr, 0, acc, B, H, W, N, Cin, 1, a.wpack, s, 1, a.wpack_valid);
+        if (route == CR_DIRECT3_S2_DGRAD) return conv3s2_dgrad_launch(dy, a.w, a.out, acc, B, H, W, Cin, N, a.wpack, s, a.wpack_valid);
+        EpStore ep{}; ep.out = a.out; ep.ld = Cin; ep.N = Cin; ep.accumulate = acc;
+        if (L == 0) return launch_conv_rows<BLTrans>(route, dy, a.w, (long)Cin, ep, M, K, Cin, s);
+        if (packed && !a.wpack_valid) launch_conv_pack(a.w, a.wpack, N, Cin, ks * ks, 1, s);      // wd[c][tap*N + n]: B(col = c, k' = tap*N + n)
+        if (L == 2) {                               // parity classes
+            const int Q = B * (H / 2) * (W / 2);
+            const ALConvT2 al{dy, H, W, Ho, Wo, N, Q};
+            ep.rm_Q = Q; ep.rm_H = H; ep.rm_W = W;
+            if (packed) return launch_conv_gemm<false>(route, al, [&](int nt) { return BLPackT2{a.wpack, N, Cin, nt}; }, ep, M, 4 * N, Cin, s);
+            return launch_conv_gemm<true>(route, al, [&](int nt) { return BLConvWT2{a.w, N, Cin, nt}; }, ep, M, 4 * N, Cin, s);
+        }
+        const ALConvT al{dy, H, W, Ho, Wo, N, ks, stride, pad};
+        if (packed) return launch_conv_gemm<false>(route, al, [&](int nt) { return BLRows{a.wpack, (long)K, Cin, nt}; }, ep, M, K, Cin, s);
+        return launch_conv_gemm<true>(route, al, [&](int nt) { return BLConvWT{a.w, N, Cin, ks * ks, nt}; }, ep, M, K, Cin, s);
+    } else if constexpr (E == CE_WGRAD) {
+        const float* x = reinterpret_cast<const float*>(a.in);
+        if (route == CR_WGRAD3) return conv3_wgrad_launch(a.dy, x, a.dw, a.ws, B, H, W, Cin, N, stride, s);
+        if (route < CR_WGRAD3) {                    // 1x1: pixel rows
+            const XRows xl{x, (long)Cin, nullptr, nullptr, nullptr, nullptr, 0, 0};
+            if (route < CR_WGRAD16) return launch_wgradw_as(route - CR_WGRADW, a.dy, (long)N, xl, a.dw, (long)Cin, a.dbias, M, N, K, s);
+            return launch_conv_wgrad16(route, a.dy, xl, a.dw, (long)Cin, a.dbias, M, N, K, s);
+        }
+        const XConvNHWC xl{x, H, W, Cin, Ho, Wo, ks, stride, pad};
+        return launch_conv_wgrad16(route, a.dy, xl, a.dw, (long)K, a.dbias, M, N, K, s);
+    } else if constexpr (E == CE_STEM_FWD) {
+        const uint8_t* x8 = reinterpret_cast<const uint8_t*>(a.in);
+        if (route / 10 * 10 == CR_STEM_FWD16) return stem_fwd_bf16_launch(a.in, a.w, a.out, B, Cin, H, W, Ho, Wo, N, s);
+        if (route / 10 * 10 == CR_STEM_FWD8) { STEM_NT(launch_stem_u8<NT>(x8, a.w, a.out, B, Cin, H, W, Ho, Wo, N, s)); }
+        const EpStore ep = conv_epilogue(a.out, N, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f);
+        const auto bl = [&](int nt) { return BLRows{a.w, (long)K, N, nt}; };
+        if (L == 3) return launch_conv_gemm<true>(route, ALStemNCHW<uint8_t>{x8, Cin, H, W, Ho, Wo, ks, stride, pad}, bl, ep, M, K, N, s);
+        return launch_conv_gemm<true>(route, ALStemNCHW<float>{reinterpret_cast<const float*>(a.in), Cin, H, W, Ho, Wo, ks, stride, pad}, bl, ep, M, K, N, s);
+    } else {
+        const uint8_t* x8 = reinterpret_cast<const uint8_t*>(a.in);
+        if (route / 10 * 10 == CR_STEM_WGRAD16) return stem_wgrad_bf16_launch(a.dy, a.in, a.dw, B, Cin, H, W, Ho, Wo, N, s);
+        if (route / 10 * 10 == CR_STEM_WGRAD8) { STEM_NT(launch_stem_u8_wgrad<NT>(a.dy, x8, a.dw, B, Cin, H, W, Ho, Wo, N, s)); }
+        if (route / 100 * 100 == CR_WGRAD16_STEM8)
+            return launch_conv_wgrad16(route, a.dy, XStemNCHW<uint8_t>{x8, Cin, H, W, Ho, Wo, ks, stride, pad}, a.dw, (long)K, nullptr, M, N, K, s);
+        return launch_conv_wgrad16(route, a.dy, XStemNCHW<float>{reinterpret_cast<const float*>(a.in), Cin, H, W, Ho, Wo, ks, stride, pad}, a.dw, (long)K, nullptr, M, N, K, s);
+    }
+}
+#undef STEM_NT
+
+// =====================================================================================================================
+// Entry points: argument check, ConvProb, conv_route, launch_conv.
+// =====================================================================================================================
+// Which kernel the entry runs for this problem in the current precision mode (include/leod_hip.h: entries, flags, codes).  Forward entries are
+// asked in the state they launch in.
+LEOD_API int leod_conv_route(int entry, int B, int H, int W, int Cin, int N, int ks, int stride, int pad, int flags, int Hp, int Wp) {
+    if (entry < 0 || entry >= CE_COUNT) return LEOD_ERR_ARG;
+    const ConvProb p = conv_prob(entry, B, H, W, Cin, N, ks, stride, pad, flags, Hp, Wp);
+    if (entry != CE_FWD && entry != CE_STEM_FWD) return conv_route(p);
+    LeodFwdScope fwd_scope;
+    return conv_route(p);
+}
+
+// y[B,Ho,Wo,N] = conv(x[B,H,W,Cin] NHWC, w[N,Cin,ks,ks]) (+bias) ; Ho = (H + 2*pad - ks)/stride + 1
+//   colstats != NULL : also accumulate per-channel (sum, sumsq) in double for training BatchNorm, spread over stat_rep
+//                      replicas [stat_rep][2][N] (power of two, zero-initialised by the caller; leod_bn_silu_fwd folds them)
+//   bn_w != NULL     : eval mode, y = silu(bn(conv)) with running statistics folded in
+LEOD_API int leod_conv_nhwc_fwd(const float* x, const float* w, const float* bias, float* y, double* colstats, int stat_rep,
+                                const float* bn_w, const float* bn_b, const float* bn_rm, const float* bn_rv, float bn_eps,
+                                int B, int H, int W, int Cin, int N, int ks, int stride, int pad, float* wpack, int wpack_valid,
+                                hipStream_t stream) {
+    LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
+    if (!x || !w || !y || (stat_rep > 1 && (stat_rep & (stat_rep - 1)))) return LEOD_ERR_ARG;
+    const ConvProb p = conv_prob(CE_FWD, B, H, W, Cin, N, ks, stride, pad,
+                                 (bias ? CF_BIAS : 0) | (colstats ? CF_COLSTATS : 0) | (bn_w ? CF_BN : 0) | (wpack ? CF_PACK : 0));
+    const ConvArgs a{x, w, bias, y, colstats, stat_rep, bn_w, bn_b, bn_rm, bn_rv, bn_eps, wpack, wpack_valid, nullptr, nullptr, nullptr, nullptr};
+    return launch_conv<CE_FWD>(conv_route(p), p, a, stream);
+}
+
+// Stem: y[B,Ho,Wo,N] = conv(pad(x[B,Cin,H,W] NCHW) , w[N,Cin,ks,ks]) with Hp,Wp the padded size
+// (Ho = (Hp + 2*pad - ks)/stride + 1).  x_is_u8: raw uint8 stacked-histogram voxels.
+static inline int stem_flags(const void* x, int x_is_u8) { return (x_is_u8 ? CF_U8 : 0) | (((uintptr_t)x & 3) == 0 ? CF_ALIGN4 : 0); }
+LEOD_API int leod_stem_conv_fwd(const void* x, int x_is_u8, const float* w, float* y, int B, int Cin, int H, int W,
+                                int Hp, int Wp, int N, int ks, int stride, int pad, hipStream_t stream) {
+    LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
+    if (!x || !w || !y) return LEOD_ERR_ARG;
+    const ConvProb p = conv_prob(CE_STEM_FWD, B, H, W, Cin, N, ks, stride, pad, stem_flags(x, x_is_u8), Hp, Wp);
+    ConvArgs a{}; a.in = x; a.w = w; a.out = y;
+    return launch_conv<CE_STEM_FWD>(conv_route(p), p, a, stream);
+}
+LEOD_API int leod_stem_conv_wgrad(const float* dy, const void* x, int x_is_u8, float* dw, int B, int Cin, int H, int W,
+                                  int Hp, int Wp, int N, int ks, int stride, int pad, hipStream_t stream) {
+    if (!dy || !x || !dw) return LEOD_ERR_ARG;
+    const ConvProb p = conv_prob(CE_STEM_WGRAD, B, H, W, Cin, N, ks, stride, pad, stem_flags(x, x_is_u8), Hp, Wp);
+    ConvArgs a{}; a.in = x; a.dy = dy; a.dw = dw;
+    return launch_conv<CE_STEM_WGRAD>(conv_route(p), p, a, stream);
+}
+
+// dx[B,H,W,Cin] (=|+=) conv_transpose(dy[B,Ho,Wo,N], w)
+LEOD_API int leod_conv_nhwc_dgrad(const float* dy, const float* w, float* dx, int accumulate, int B, int H, int W, int Cin,
+                                  int N, int ks, int stride, int pad, float* wpack, int wpack_valid, hipStream_t stream) {
+    if (!dy || !w || !dx) return LEOD_ERR_ARG;
+    const ConvProb p = conv_prob(CE_DGRAD, B, H, W, Cin, N, ks, stride, pad, (wpack ? CF_PACK : 0) | (accumulate ? CF_ACCUMULATE : 0));
+    ConvArgs a{}; a.in = dy; a.w = w; a.out = dx; a.wpack = wpack; a.wpack_valid = wpack_valid;
+    return launch_conv<CE_DGRAD>(conv_route(p), p, a, stream);
+}
+
+// dw[N,Cin,ks,ks] += dy^T im2col(x) ; dbias[N] += colsum(dy)
+// floats of workspace leod_conv_nhwc_wgrad wants for this shape in the current precision mode (0: none)
+LEOD_API long leod_conv_nhwc_wgrad_workspace_floats(int B, int H, int W, int Cin, int N, int ks, int stride, int pad, int has_bias) {
+    const int route = conv_route(conv_prob(CE_WGRAD, B, H, W, Cin, N, ks, stride, pad, CF_WS | (has_bias ? CF_DBIAS : 0)));
+    return route == CR_WGRAD3 ? (long)conv3_wgrad_workspace_floats(B, H, W, Cin, N, stride) : 0;
+}
+LEOD_API int leod_conv_nhwc_wgrad(const float* dy, const float* x, float* dw, float* dbias, float* ws, int B, int H, int W, int Cin,
+                                  int N, int ks, int stride, int pad, hipStream_t stream) {
+    if (!dy || !x || !dw) return LEOD_ERR_ARG;
+    const ConvProb p = conv_prob(CE_WGRAD, B, H, W, Cin, N, ks, stride, pad, (ws ? CF_WS : 0) | (dbias ? CF_DBIAS : 0));
+    ConvArgs a{}; a.in = x; a.dy = dy; a.dw = dw; a.dbias = dbias; a.ws = ws;
+    return launch_conv<CE_WGRAD>(conv_route(p), p, a, stream);
+}
+
 // ---- grouped 3x3 / stride-1 / pad-1 convolutions: n <= 8 independent problems of ONE channel geometry in one launch (k_conv3.hip, C3Group) ----
 // The convs of equal depth in the cls / reg towers of the three head levels (yolo_head.py:61-145 of the reference builds them as separate
 // modules; yolo_head.py:208-222 runs them level by level).  Arrays are HOST arrays of length n.  -3: not coverable (run the problems singly).
-// 1: leod_conv3x3_group_fwd covers these n maps for Cin -> Cout in the current precision mode (callers ask BEFORE they hand out weight-pack
-// buffers: a refused call must not leave a pack marked valid); the dgrad of the same convs: ask with (Cout, Cin)
+// 1: leod_conv3x3_group_fwd covers these n maps for Cin -> Cout in the current precision mode: every member routes to the direct kernel; the
+// dgrad of the same convs: ask with (Cout, Cin)
 LEOD_API int leod_conv3x3_group_supported(int n, const int* H, const int* W, int Cin, int Cout) {
-    return (H && W && conv3s1_group_supported(n, H, W, Cin, Cout)) ? 1 : 0;
+    return conv_group_routes_to(CR_DIRECT3 + 10, CE_FWD, CF_PACK, n, H, W, Cin, Cout) ? 1 : 0;
 }
 LEOD_API int leod_conv3x3_group_fwd(int n, const float* const* x, const float* const* w, float* const* y, double* const* colstats,
                                     const int* stat_rep, void* const* wpack, const int* wpack_valid, const int* B, const int* H, const int* W,
                                     int Cin, int Cout, hipStream_t stream) {
     if (n < 1 || n > 8 || !x || !w || !y || !colstats || !stat_rep || !wpack || !wpack_valid || !B || !H || !W) return LEOD_ERR_ARG;
     for (int k = 0; k < n; ++k) if (!x[k] || !w[k] || !y[k] || !wpack[k]) return LEOD_ERR_ARG;
-    if (!conv3s1_group_supported(n, H, W, Cin, Cout)) return LEOD_ERR_UNSUPPORTED;
     LeodFwdScope fwd_scope;
+    if (!conv_group_routes_to(CR_DIRECT3 + 10, CE_FWD, CF_PACK, n, H, W, Cin, Cout)) return LEOD_ERR_UNSUPPORTED;
     int zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     return conv3s1_group(n, x, w, y, colstats, stat_rep, zeros, B, H, W, Cin, Cout, 0, wpack, wpack_valid, stream);
 }
@@ -554,7 +549,7 @@ LEOD_API int leod_conv3x3_group_dgrad(int n, const float* const* dy, const float
         if (!dy[k] || !w[k] || !dx[k] || !wpack[k]) return LEOD_ERR_ARG;
         for (int j = 0; j < k; ++j) if (dx[j] == dx[k]) return LEOD_ERR_ARG;
     }
-    if (!conv3s1_group_supported(n, H, W, N, Cin)) return LEOD_ERR_UNSUPPORTED;
+    if (!conv_group_routes_to(CR_DIRECT3 + 10, CE_DGRAD, CF_PACK, n, H, W, Cin, N)) return LEOD_ERR_UNSUPPORTED;
     double* nostats[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     return conv3s1_group(n, dy, w, dx, nostats, zeros, accumulate, B, H, W, N, Cin, 1, wpack, wpack_valid, stream);
@@ -563,40 +558,12 @@ LEOD_API int leod_conv3x3_group_dgrad(int n, const float* const* dy, const float
 // dw_k [N,Cin,3,3] += weight gradient of y_k = conv3x3(x_k [B,H,W,Cin], w_k) from dy_k [B,H,W,N] (stride 1), n <= 8 problems of one geometry in
 // one launch + one reduce launch.  ws[k]: leod_conv3x3_group_wgrad_workspace_floats(B[k], H[k], W[k], Cin, N) floats (0: not coverable)
 LEOD_API long leod_conv3x3_group_wgrad_workspace_floats(int B, int H, int W, int Cin, int N) {
-    return conv3_wgrad_supported(H, W, Cin, N, 1) ? (long)conv3_wgrad_group_workspace_floats(B, H, W, Cin, N, 1) : 0;
+    return conv_group_routes_to(CR_WGRAD3, CE_WGRAD, CF_WS, 1, &H, &W, Cin, N) ? (long)conv3_wgrad_group_workspace_floats(B, H, W, Cin, N, 1) : 0;
 }
 LEOD_API int leod_conv3x3_group_wgrad(int n, const float* const* dy, const float* const* x, float* const* dw, float* const* ws, const int* B,
                                       const int* H, const int* W, int Cin, int N, hipStream_t stream) {
     if (n < 1 || n > 8 || !dy || !x || !dw || !ws || !B || !H || !W) return LEOD_ERR_ARG;
-    for (int k = 0; k < n; ++k) {
-        if (!dy[k] || !x[k] || !dw[k] || !ws[k]) return LEOD_ERR_ARG;
-        if (!conv3_wgrad_supported(H[k], W[k], Cin, N, 1)) return LEOD_ERR_UNSUPPORTED;
-    }
+    for (int k = 0; k < n; ++k) if (!dy[k] || !x[k] || !dw[k] || !ws[k]) return LEOD_ERR_ARG;
+    if (!conv_group_routes_to(CR_WGRAD3, CE_WGRAD, CF_WS, n, H, W, Cin, N)) return LEOD_ERR_UNSUPPORTED;
     return conv3_wgrad_group_launch(n, dy, x, dw, ws, B, H, W, Cin, N, 1, stream, true);
-}
-
-LEOD_API int leod_stem_conv_wgrad(const float* dy, const void* x, int x_is_u8, float* dw, int B, int Cin, int H, int W,
-                                  int Hp, int Wp, int N, int ks, int stride, int pad, hipStream_t stream) {
-    if (!dy || !x || !dw) return LEOD_ERR_ARG;
-    if (ks < 1 || ks > 15) return LEOD_ERR_UNSUPPORTED;
-    const int Ho = (Hp + 2 * pad - ks) / stride + 1, Wo = (Wp + 2 * pad - ks) / stride + 1;
-    const int M = B * Ho * Wo, K = Cin * ks * ks;
-    static const int stem_patch = 1;
-    if (stem_patch && ks == 7 && x_is_u8 && leod_precision() == 1 && stem_wgrad_bf16_supported(x, Cin, H, W, N, stride, pad))
-        return stem_wgrad_bf16_launch(dy, x, dw, B, Cin, H, W, Ho, Wo, N, stream);     // k_stem.hip
-    if (stem_patch && ks == 7 && x_is_u8 && stride == 4 && pad == 3 && N <= 64 && !(N & 15) && !(W & 3) && Cin * 19 * 18 <= 27 * 256 &&
-        ((uintptr_t)x & 3) == 0 && ((long)Cin * H * W) % 4 == 0) {
-        switch (N / 16) {
-            case 1: return launch_stem_u8_wgrad<1>(dy, (const uint8_t*)x, dw, B, Cin, H, W, Ho, Wo, N, stream);
-            case 2: return launch_stem_u8_wgrad<2>(dy, (const uint8_t*)x, dw, B, Cin, H, W, Ho, Wo, N, stream);
-            case 3: return launch_stem_u8_wgrad<3>(dy, (const uint8_t*)x, dw, B, Cin, H, W, Ho, Wo, N, stream);
-            default: return launch_stem_u8_wgrad<4>(dy, (const uint8_t*)x, dw, B, Cin, H, W, Ho, Wo, N, stream);
-        }
-    }
-    if (x_is_u8) {
-        XStemNCHW<uint8_t> xl{(const uint8_t*)x, Cin, H, W, Ho, Wo, ks, stride, pad};
-        return wgrad_any(dy, xl, dw, (long)K, nullptr, M, N, K, stream);
-    }
-    XStemNCHW<float> xl{(const float*)x, Cin, H, W, Ho, Wo, ks, stride, pad};
-    return wgrad_any(dy, xl, dw, (long)K, nullptr, M, N, K, stream);
 }

@@ -842,12 +842,6 @@ int conv3s1_group(int n, const float* const* x, const float* const* w, float* co
     const BnEval none{nullptr, nullptr, nullptr, nullptr, 0.f};
     return conv3s1_group_launch(n, x, w, y, colstats, stat_rep, accumulate, B, H, W, Cin, Cout, transposed, wpack, packed, stream, 1, none);
 }
-bool conv3s1_group_supported(int n, const int* H, const int* W, int Cin, int Cout) {
-    if (n < 1 || n > 8) return false;
-    for (int k = 0; k < n; ++k)
-        if (!conv3s1_supported(H[k], W[k], Cin, Cout)) return false;
-    return true;
-}
 
 // shapes of the direct weight-gradient kernel: stride 1 or 2 (even H, W), output channels in slices of 96, input channels 48 or in
 // slices of 96
@@ -871,10 +865,7 @@ bool conv3_wgrad_supported(int H, int W, int Cin, int Cout, int stride) {
 
 // the 8-wave / nine-tap kernel takes everything but the smallest problems (a few regions: the three kernel-row workgroups of
 // conv3_wgrad_kernel fill more CUs; 96 -> 96 on the 8 x 10 level: 17 vs 21 us)
-static inline bool conv3_wgrad_nine(int nregions, int nslices) {
-    static const int on = 1;
-    return on && nregions * nslices > 32;
-}
+static inline bool conv3_wgrad_nine(int nregions, int nslices) { return nregions * nslices > 32; }
 static inline Conv3WgradPlan conv3_wgrad_plan(int B, int H, int W, int Cin, int Cout, int S, bool force_nine) {
     Conv3WgradPlan pl{};
     const int Ho = H / S, Wo = W / S;
@@ -921,8 +912,7 @@ static inline Conv3WgradPlan conv3_wgrad_plan(int B, int H, int W, int Cin, int 
         // 9-tap workgroups, one per CU (LDS): slices * workers of them, and each writes a whole 9 x 96 x CI slice of partial sums that
         // the reduce kernel reads back -- 256 workgroups when each gets >= 2 regions (the backbone convs on 168 frames: stage 2
         // 174 -> 103 us, stage 3 141 -> 69, stage 4 169 -> 74), 128 for the PAFPN / head convs on the 32 labelled frames (38 vs 43 us)
-        static const int fill9 = 0;
-        const int target = fill9 ? fill9 : (nregions * pl.nslices >= 512 ? 256 : 128);
+        const int target = nregions * pl.nslices >= 512 ? 256 : 128;
         workers = max(1, target / pl.nslices);
     }
     pl.workers = min(nregions, workers);

@@ -358,7 +358,6 @@ int launch_fwd(const uint8_t* x, const float* w, float* y, int B, int H, int W, 
     constexpr int KS = (CIN * 7 + 3) >> 2, LDW = KS * 32 + 16;
     const size_t lds = (size_t)16 * NT * LDW * 2 + (size_t)CIN * PR * RS * 2;
     static const int workers = 256;
-    static const int dbg = 0;
     int gx = ntiles < workers ? ntiles : workers;
     if (gx >= 8) gx &= ~7;                                     // whole XCD rounds (see the tile order of the kernel)
     LEOD_BY_OPFMT16({
@@ -368,17 +367,16 @@ int launch_fwd(const uint8_t* x, const float* w, float* y, int B, int H, int W, 
             leod_register_input_kernel(reinterpret_cast<const void*>(&stem_fwd_bf16_kernel<NT, CIN, PD, OF>), 0, 12);
             attr = true;
         }
-        hipLaunchKernelGGL((stem_fwd_bf16_kernel<NT, CIN, PD, OF>), dim3(gx), dim3(512), lds, s, x, w, y, B, H, W, Ho, Wo, N, tiles_x, tiles_y, dbg);
+        hipLaunchKernelGGL((stem_fwd_bf16_kernel<NT, CIN, PD, OF>), dim3(gx), dim3(512), lds, s, x, w, y, B, H, W, Ho, Wo, N, tiles_x, tiles_y, /* dbg: every stage on */ 0);
     });
     return leod_launch_status();
 }
 
 }  // namespace
 
-bool stem_wgrad_bf16_supported(const void* x, int Cin, int H, int W, int N, int stride, int pad) {
-    static const int on = 1;
-    return on && stride == 4 && pad == 3 && N >= 16 && N <= 64 && !(N & 15) && !(W & 3) && Cin * PR * RD <= RX * 512 &&
-           Cin * 7 <= 2 * 8 * KT && ((uintptr_t)x & 3) == 0 && ((long)Cin * H * W) % 4 == 0;
+bool stem_wgrad_bf16_supported(bool x_aligned4, int Cin, int H, int W, int N, int stride, int pad) {
+    return stride == 4 && pad == 3 && N >= 16 && N <= 64 && !(N & 15) && !(W & 3) && Cin * PR * RD <= RX * 512 &&
+           Cin * 7 <= 2 * 8 * KT && x_aligned4 && ((long)Cin * H * W) % 4 == 0;
 }
 
 int stem_wgrad_bf16_launch(const float* dy, const void* x, float* dW, int B, int Cin, int H, int W, int Ho, int Wo, int N,
@@ -393,9 +391,8 @@ int stem_wgrad_bf16_launch(const float* dy, const void* x, float* dW, int B, int
 
 // forward: the 20 event-representation channels of every RVT configuration; weights of all N channels (16 NT x 35 x 32 + pad bf16) and
 // the patch fill the 160 KB of LDS (N = 64, RVT-B, does not fit: it stays on stem_u8_fwd_kernel)
-bool stem_fwd_bf16_supported(const void* x, int Cin, int H, int W, int N, int stride, int pad) {
-    static const int on = 1;
-    return on && stride == 4 && pad == 3 && Cin == 20 && (N == 32 || N == 48) && !(W & 3) && ((uintptr_t)x & 3) == 0 &&
+bool stem_fwd_bf16_supported(bool x_aligned4, int Cin, int H, int W, int N, int stride, int pad) {
+    return stride == 4 && pad == 3 && Cin == 20 && (N == 32 || N == 48) && !(W & 3) && x_aligned4 &&
            ((long)Cin * H * W) % 4 == 0;
 }
 

@@ -7,24 +7,6 @@
 #define LEOD_SHADOW_KERNELS 1        // bf16-shadow weight loaders for the Linear layers (gemm16.hpp: BLRows16 / BLTrans16)
 #include "gemm16.hpp"
 
-static inline int pick_nt(int N) {
-    int best = 1; long bestpad = 1L << 60;
-    for (int nt = 4; nt >= 1; --nt) {
-        const long pad = (long)cdiv(N, 16 * nt) * 16 * nt;
-        if (pad < bestpad) { bestpad = pad; best = nt; }
-    }
-    return best;
-}
-
-#define DISPATCH_NT(NTV, ...)                                          \
-    switch (NTV) {                                                     \
-        case 1: { constexpr int NT = 1; __VA_ARGS__; } break;          \
-        case 2: { constexpr int NT = 2; __VA_ARGS__; } break;          \
-        case 3: { constexpr int NT = 3; __VA_ARGS__; } break;          \
-        default: { constexpr int NT = 4; __VA_ARGS__; } break;         \
-    }
-
-
 static inline EpStore ep_store(float* out, long ld, int N) {
     EpStore e{};
     e.out = out; e.ld = ld; e.N = N; e.act = ACT_NONE;

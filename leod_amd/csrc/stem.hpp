@@ -2,8 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-bool stem_wgrad_bf16_supported(const void* x, int Cin, int H, int W, int N, int stride, int pad);
+// x_aligned4: the input address is a multiple of 4
+bool stem_wgrad_bf16_supported(bool x_aligned4, int Cin, int H, int W, int N, int stride, int pad);
 int stem_wgrad_bf16_launch(const float* dy, const void* x, float* dW, int B, int Cin, int H, int W, int Ho, int Wo, int N,
                            hipStream_t s);
-bool stem_fwd_bf16_supported(const void* x, int Cin, int H, int W, int N, int stride, int pad);
+bool stem_fwd_bf16_supported(bool x_aligned4, int Cin, int H, int W, int N, int stride, int pad);
 int stem_fwd_bf16_launch(const void* x, const float* w, float* y, int B, int Cin, int H, int W, int Ho, int Wo, int N, hipStream_t s);

@@ -557,9 +557,9 @@ def linear_wgrad_group(problems) -> bool:
         _wgrad_workspace(problems[0]['dW'].device)
     ev = _probe('linear_wgrad', nb, fl, rows=M, nbytes16=nb16)
     rc = _l().leod_linear_wgrad_group(n, _ptr_array([p['dy'] for p in problems]), _int_array(dyf), _ptr_array([p['x'] for p in problems]), _int_array(xf),
-                                      _ptr_array_opt([p.get('stats') for p in problems]), _ptr_array_opt([p.get('ln_w') for p in problems]),
-                                      _ptr_array_opt([p.get('ln_b') for p in problems]), _ptr_array([p['dW'] for p in problems]),
-                                      _ptr_array_opt([p.get('dbias') for p in problems]), M, _int_array(Ns), _int_array(Ks), _stream())
+                                      _ptr_array([p.get('stats') for p in problems]), _ptr_array([p.get('ln_w') for p in problems]),
+                                      _ptr_array([p.get('ln_b') for p in problems]), _ptr_array([p['dW'] for p in problems]),
+                                      _ptr_array([p.get('dbias') for p in problems]), M, _int_array(Ns), _int_array(Ks), _stream())
     if rc == -3:
         if ev is not None:
             _PROBE.cancel('linear_wgrad')
@@ -764,6 +764,33 @@ class PackCache:
         cls.epoch += 1
 
 
+# flags of ``conv_route``: what the call is given (include/leod_hip.h, leod_conv_route)
+CF_BIAS, CF_COLSTATS, CF_BN, CF_PACK, CF_WS, CF_DBIAS, CF_ACCUMULATE, CF_U8, CF_ALIGN4 = 1, 2, 4, 8, 16, 32, 64, 128, 256
+_CONV_ROUTES = {}
+
+
+def conv_route(entry, B, H, W, Cin, N, ks=3, stride=1, pad=None, flags=0, padded_hw=None) -> int:
+    """The kernel dense-convolution call number ``entry`` (0 conv_nhwc_fwd, 1 conv_nhwc_dgrad, 2 conv_nhwc_wgrad, 3 stem_conv_fwd,
+    4 stem_conv_wgrad) runs for this problem in the current precision mode, or the negative error code it returns (``leod_conv_route`` in
+    include/leod_hip.h lists the flags and the route codes; nothing is launched).  pad defaults to (ks - 1) // 2, the stem's padded frame
+    to its stored one.  Answers are remembered per precision mode (``leod_conv_route`` reads nothing but its arguments and the mode): the
+    conv wrappers ask on every call, and a repeated question must not cost the eager step a C call that a launch probe brackets."""
+    pad = (ks - 1) // 2 if pad is None else pad
+    key = (int(_l().leod_get_precision()), entry, B, H, W, Cin, N, ks, stride, pad, flags, padded_hw)
+    code = _CONV_ROUTES.get(key)
+    if code is None:
+        if len(_CONV_ROUTES) > 4096:
+            _CONV_ROUTES.clear()
+        hp, wp = padded_hw if padded_hw is not None else (0, 0)
+        code = _CONV_ROUTES[key] = int(_l().leod_conv_route(entry, B, H, W, Cin, N, ks, stride, pad, flags, hp, wp))
+    return code
+
+
+def conv_route_reads_pack(code: int) -> bool:
+    """the routes that read ``wpack``: the direct 3x3 kernels (per-tap 16-bit pack) and the LDS-staged GEMM on the K-contiguous fp32 pack"""
+    return code in (110, 120, 220) or (code >= 10000 and code % 10000 // 1000 == 7)
+
+
 def _is_depthwise(w, cin: int) -> bool:
     """a conv weight [C,1,ks,ks] over a C-channel map (C > 1) is a depthwise convolution (nn.Conv2d(C, C, ks, groups=C))"""
     return w.dim() == 4 and w.shape[1] == 1 and cin > 1 and w.shape[0] == cin
@@ -791,7 +818,10 @@ def conv_nhwc_fwd(x, w, bias=None, stride=1, colstats=None, bn=None, bn_eps=1e-5
         check(_l().leod_dwconv_nhwc_fwd(_p(x), _p(w), _p(bias), _p(y), _p(colstats), rep, _p(bw), _p(bb), _p(brm), _p(brv), bn_eps,
                                          B, H, W, Cin, ks, stride, pad, _stream()), 'dwconv_nhwc_fwd')
         return y
-    wpack, valid = PackCache.get(w, ('fwd', B, H, W, stride, bn is not None, bias is not None), N * Cin * ks * ks) if ks > 1 else (None, 0)
+    flags = (CF_PACK if ks > 1 else 0) | (CF_BIAS if bias is not None else 0) | (CF_COLSTATS if colstats is not None else 0) | (CF_BN if bn is not None else 0)
+    wpack, valid = None, 0                        # a pack buffer is offered to ks > 1 only, and taken only for the routes that read one
+    if conv_route_reads_pack(conv_route(0, B, H, W, Cin, N, ks, stride, pad, flags)):
+        wpack, valid = PackCache.get(w, ('fwd', B, H, W, stride, bn is not None, bias is not None), N * Cin * ks * ks)
     rep = colstats.shape[0] if colstats is not None and colstats.dim() == 3 else 1
     check(_l().leod_conv_nhwc_fwd(_p(x), _p(w), _p(bias), _p(y), _p(colstats), rep, _p(bw), _p(bb), _p(brm), _p(brv), bn_eps,
                                    B, H, W, Cin, N, ks, stride, pad, _p(wpack), valid, _stream()), 'conv_nhwc_fwd')
@@ -812,14 +842,18 @@ def conv_nhwc_dgrad(dy, w, x_shape, stride=1, out=None, accumulate=False):
         check(_l().leod_dwconv_nhwc_dgrad(_p(dy), _p(w), _p(out), 1 if accumulate else 0, B, H, W, Cin, ks, stride, pad, _stream()),
               'dwconv_nhwc_dgrad')
         return out
-    wpack, valid = PackCache.get(w, ('dgrad', B, H, W, stride), N * Cin * ks * ks) if ks > 1 else (None, 0)
+    wpack, valid = None, 0
+    if conv_route_reads_pack(conv_route(1, B, H, W, Cin, N, ks, stride, pad, CF_PACK if ks > 1 else 0)):
+        wpack, valid = PackCache.get(w, ('dgrad', B, H, W, stride), N * Cin * ks * ks)
     check(_l().leod_conv_nhwc_dgrad(_p(dy), _p(w), _p(out), 1 if accumulate else 0, B, H, W, Cin, N, ks, stride, pad,
                                      _p(wpack), valid, _stream()), 'conv_nhwc_dgrad')
     return out
 
 
-def _int_array(v):
-    return (ctypes.c_int * len(v))(*[int(a) for a in v])
+def _conv3x3_group_routes_to(code, entry, flags, shapes, Cin, N) -> bool:
+    """1..8 stride-1 3x3 problems of one channel geometry share a launch when every member routes to ``code`` (a refused grouped call must
+    not have touched the pack cache: a pack marked valid there would never have been written)"""
+    return 1 <= len(shapes) <= 8 and all(conv_route(entry, sh[0], sh[1], sh[2], Cin, N, 3, 1, 1, flags) == code for sh in shapes)
 
 
 def conv3x3_group_ok(xs, ws) -> bool:
@@ -838,8 +872,8 @@ def conv3x3_group_fwd(xs, ws, colstats):
     for c in colstats:
         _ck(c, torch.float64, 'colstats')
     N, Cin = ws[0].shape[0], ws[0].shape[1]
-    if not _l().leod_conv3x3_group_supported(n, _int_array([x.shape[1] for x in xs]), _int_array([x.shape[2] for x in xs]), Cin, N):
-        return None                                           # asked before any pack buffer is handed out (a refused call must not leave one marked valid)
+    if not _conv3x3_group_routes_to(110, 0, CF_PACK | CF_COLSTATS, [x.shape for x in xs], Cin, N):
+        return None
     ys = [_empty(tuple(x.shape[:3]) + (N,), x) for x in xs]
     packs = [PackCache.get(w, ('fwd', x.shape[0], x.shape[1], x.shape[2], 1, False, False), N * Cin * 9) for x, w in zip(xs, ws)]
     rc = _l().leod_conv3x3_group_fwd(n, _ptr_array(xs), _ptr_array(ws), _ptr_array(ys), _ptr_array(colstats),
@@ -856,7 +890,7 @@ def conv3x3_group_dgrad(dys, ws, x_shapes, outs, accumulate) -> bool:
     for t in list(dys) + list(ws) + list(outs):
         _ck(t, name='conv3x3_group')
     N, Cin = ws[0].shape[0], ws[0].shape[1]
-    if not _l().leod_conv3x3_group_supported(n, _int_array([sh[1] for sh in x_shapes]), _int_array([sh[2] for sh in x_shapes]), N, Cin):
+    if not _conv3x3_group_routes_to(110, 1, CF_PACK, x_shapes, Cin, N):
         return False
     packs = [PackCache.get(w, ('dgrad', sh[0], sh[1], sh[2], 1), N * Cin * 9) for w, sh in zip(ws, x_shapes)]
     rc = _l().leod_conv3x3_group_dgrad(n, _ptr_array(dys), _ptr_array(ws), _ptr_array(outs), _int_array([1 if a else 0 for a in accumulate]),
@@ -872,9 +906,9 @@ def conv3x3_group_wgrad(dys, xs, dws) -> bool:
     for t in list(dys) + list(xs) + list(dws):
         _ck(t, name='conv3x3_group')
     N, Cin = dws[0].shape[0], dws[0].shape[1]
-    sizes = [int(_l().leod_conv3x3_group_wgrad_workspace_floats(x.shape[0], x.shape[1], x.shape[2], Cin, N)) for x in xs]
-    if not all(sizes):
+    if not _conv3x3_group_routes_to(500, 2, CF_WS, [x.shape for x in xs], Cin, N):
         return False
+    sizes = [int(_l().leod_conv3x3_group_wgrad_workspace_floats(x.shape[0], x.shape[1], x.shape[2], Cin, N)) for x in xs]
     ws = _empty((sum(sizes),), dys[0])
     parts, off = [], 0
     for sz in sizes:
@@ -882,8 +916,6 @@ def conv3x3_group_wgrad(dys, xs, dws) -> bool:
         off += sz
     rc = _l().leod_conv3x3_group_wgrad(n, _ptr_array(dys), _ptr_array(xs), _ptr_array(dws), _ptr_array(parts), _int_array([x.shape[0] for x in xs]),
                                        _int_array([x.shape[1] for x in xs]), _int_array([x.shape[2] for x in xs]), Cin, N, _stream())
-    if rc == -3:
-        return False
     check(rc, 'conv3x3_group_wgrad')
     return True
 
@@ -917,8 +949,8 @@ def bn_silu_fwd(z, colstats, w, b, run_mean, run_var, count, eps=1e-5, momentum=
     return y, mean, rstd
 
 
-def _ptr_array_opt(ts):
-    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+def _int_array(v):
+    return (ctypes.c_int * len(v))(*[int(a) for a in v])
 
 
 def _f64_array(v):
@@ -941,10 +973,10 @@ def bn_silu_fwd_group(zs, colstats, ws, bs, run_means, run_vars, counts, eps, mo
     ys = [_empty(z_.shape, z_) for z_ in zs]
     means = [_empty((N,), z_) for z_ in zs]
     rstds = [_empty((N,), z_) for z_ in zs]
-    cd = None if count_devs is None or all(c is None for c in count_devs) else _ptr_array_opt(count_devs)
+    cd = None if count_devs is None or all(c is None for c in count_devs) else _ptr_array(count_devs)
     check(_l().leod_bn_silu_fwd_group(n, _ptr_array(zs), _ptr_array(colstats), _int_array([c.shape[0] if c.dim() == 3 else 1 for c in colstats]),
                                        _ptr_array(ws), _ptr_array(bs), _ptr_array(ys), _ptr_array(means), _ptr_array(rstds),
-                                       _ptr_array_opt(run_means), _ptr_array_opt(run_vars), _int_array([z_.numel() // N for z_ in zs]), N,
+                                       _ptr_array(run_means), _ptr_array(run_vars), _int_array([z_.numel() // N for z_ in zs]), N,
                                        _f64_array(counts), cd, float(eps), _f32_array(momenta), _stream()), 'bn_silu_fwd_group')
     return list(zip(ys, means, rstds))
 
@@ -969,7 +1001,7 @@ def bn_silu_bwd_apply_group(dys, zs, means, rstds, ws, bs, sums, dws, dbs, count
     if not all(lds):
         raise LeodHipError('bn_silu_bwd_apply_group: dy must be contiguous or a channel slice of a contiguous map')
     dzs = [_empty(z_.shape, z_) for z_ in zs]
-    cd = None if count_devs is None or all(c is None for c in count_devs) else _ptr_array_opt(count_devs)
+    cd = None if count_devs is None or all(c is None for c in count_devs) else _ptr_array(count_devs)
     check(_l().leod_bn_silu_bwd_apply_group(n, _ptr_array(dys), _ptr_array(zs), _ptr_array(means), _ptr_array(rstds), _ptr_array(ws), _ptr_array(bs),
                                              _ptr_array(sums), _int_array([o.shape[0] if o.dim() == 3 else 1 for o in sums]), _ptr_array(dzs),
                                              _ptr_array(dws), _ptr_array(dbs), _int_array([z_.numel() // N for z_ in zs]), N, _f64_array(counts), cd,
@@ -1082,10 +1114,6 @@ def bn_silu_bwd_apply(dy, z, mean, rstd, w, b, sums, dw, db, count, count_dev=No
 # ---------------------------------------------------------------------------------------------------
 # head tail
 # ---------------------------------------------------------------------------------------------------
-def _iarr(v: Sequence[int]):
-    return (ctypes.c_int * len(v))(*[int(a) for a in v])
-
-
 def head_pred_fwd(cls_feat, reg_feat, cls_w, cls_b, reg_w, reg_b, obj_w, obj_b, out_train, out_infer, stride, a0):
     for t in (cls_feat, reg_feat, cls_w, cls_b, reg_w, reg_b, obj_w, obj_b, out_train, out_infer):
         _ck(t, name='head_pred')
@@ -1128,8 +1156,8 @@ def simota_assign(outputs, labels, hws, strides, ignore_label=1024.0):
              totals=StatArena.zeros((3,), dev, torch.int32))
     check(_l().leod_simota_assign(_p(outputs), _p(labels), _p(ws), _p(r['fg_mask']), _p(r['ignore_mask']),
                                    _p(r['matched_row']), _p(r['matched_valid_idx']), _p(r['pred_iou']), _p(r['num_fg_img']),
-                                   _p(r['totals']), B, Nmax, nch - 5, len(hws), _iarr([h for h, _ in hws]),
-                                   _iarr([w for _, w in hws]), _iarr(strides), float(ignore_label), _stream()),
+                                   _p(r['totals']), B, Nmax, nch - 5, len(hws), _int_array([h for h, _ in hws]),
+                                   _int_array([w for _, w in hws]), _int_array(strides), float(ignore_label), _stream()),
           'simota_assign')
     return r
 
@@ -1159,14 +1187,14 @@ def yolox_loss(outputs, labels, assign, hws, strides, want_grad=True, focal=Fals
         check(_l().leod_yolox_loss_weighted(_p(outputs), _p(labels), _p(assign['fg_mask']), _p(assign['ignore_mask']),
                                              _p(assign['matched_row']), _p(assign['pred_iou']), _p(assign['totals']), _p(label_w),
                                              _p(wsum), _p(sums), _p(losses), _p(d_raw), B, labels.shape[1], nch - 5, len(hws),
-                                             _iarr([h for h, _ in hws]), _iarr([w for _, w in hws]), _iarr(strides),
+                                             _int_array([h for h, _ in hws]), _int_array([w for _, w in hws]), _int_array(strides),
                                              1 if focal else 0, reg_weight, obj_weight, cls_weight, grad_scale, _stream()),
               'yolox_loss_weighted')
         return losses, d_raw
     check(_l().leod_yolox_loss(_p(outputs), _p(labels), _p(assign['fg_mask']), _p(assign['ignore_mask']),
                                 _p(assign['matched_row']), _p(assign['pred_iou']), _p(assign['totals']), _p(sums), _p(losses),
-                                _p(d_raw), B, labels.shape[1], nch - 5, len(hws), _iarr([h for h, _ in hws]),
-                                _iarr([w for _, w in hws]), _iarr(strides), 1 if focal else 0, reg_weight, obj_weight,
+                                _p(d_raw), B, labels.shape[1], nch - 5, len(hws), _int_array([h for h, _ in hws]),
+                                _int_array([w for _, w in hws]), _int_array(strides), 1 if focal else 0, reg_weight, obj_weight,
                                 cls_weight, grad_scale, _stream()), 'yolox_loss')
     return losses, d_raw
 
@@ -1384,12 +1412,11 @@ def weight_shadow_pin(on: bool) -> None:
 
 
 def _ptr_array(ts):
-    import ctypes
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    """host array of device addresses; None entries become NULL"""
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
 
 def _long_array(v):
-    import ctypes
     return (ctypes.c_long * len(v))(*[int(x) for x in v])
 
 

@@ -266,6 +266,50 @@ def test_conv3x3_strided_sliced_direct_bf16(bf16_ops, B, H, W, Cin, N, stride):
     tk.close(dw, 2 * w.grad, what='conv3x3 wgrad (direct) accumulates')
 
 
+# every (entry, route) pair of ops.conv_route that launches in the 16-bit modes, at the smallest shape that reaches it (rows as in
+# test_kernels_gpu.CONV_ROUTE_CASES_F32): the direct 3x3 kernels (110 / 120 / 220 / 500) run at 1 x 4 x 4 x 48, wgradw (300 + c) from 8192 rows,
+# its 16-row-chunk configuration (305) past 65536; the wide tiles (3000 + 10 NT + NTW) from 4096 rows and 144 columns
+CONV_ROUTE_CASES_16 = [
+    (1, 4, 4, 16, 32, 1, 1, False, True, (6021, 6011, 424)), (1, 4, 4, 16, 32, 3, 1, False, True, (19024, 19014, 724)),
+    (1, 4, 4, 64, 128, 1, 1, False, True, (6041, 6044, 444)), (1, 8, 8, 16, 16, 3, 2, False, True, (19014, 29011, 714)),
+    (1, 4, 4, 48, 48, 3, 1, True, True, (19034, 110, 734)), (1, 4, 4, 48, 48, 3, 1, False, True, (110, 110, 734)),
+    (2, 64, 64, 16, 16, 1, 1, False, True, (6011, 6011, 301)), (1, 8, 8, 48, 96, 3, 2, False, True, (120, 220, 500)),
+    (68, 5, 7, 36, 100, 1, 1, False, True, (5164, 6031, 414)), (1, 8, 8, 96, 192, 3, 2, False, False, (19044, 29034, 500)),
+    (2, 64, 64, 16, 160, 1, 1, False, True, (5264, 6014, 302)), (17, 32, 32, 64, 32, 1, 1, False, True, (5264, 4464, 303)),
+    (9, 2, 324, 192, 48, 1, 1, False, True, (6034, 4448, 434)), (17, 32, 32, 36, 100, 1, 1, False, True, (5164, 4364, 302)),
+    (2, 64, 64, 96, 192, 1, 1, False, True, (3043, 4348, 304)), (17, 64, 64, 16, 16, 3, 2, False, True, (17148, 27164, 714)),
+    (17, 32, 32, 32, 64, 3, 1, False, True, (17448, 17248, 744)), (17, 32, 32, 64, 32, 3, 2, False, True, (19024, 27464, 724)),
+    (2, 64, 64, 48, 96, 3, 1, False, False, (18348, 19034, 734)), (2, 64, 64, 48, 96, 3, 1, True, True, (17348, 110, 734)),
+    (17, 32, 32, 48, 48, 3, 2, False, False, (19034, 28348, 734)), (17, 32, 32, 48, 48, 3, 2, False, True, (19034, 27348, 734)),
+    (17, 64, 64, 20, 32, 3, 2, False, True, (17264, 27264, 724)), (17, 32, 32, 36, 100, 3, 1, False, True, (17164, 17364, 714)),
+    (1, 64, 64, 32, 256, 1, 1, False, True, (3044, 6024, 444)), (17, 64, 64, 96, 96, 1, 1, False, True, (4348, 4348, 305)),
+    (1, 4, 4, 96, 96, 3, 1, False, True, (110, 110, 500)),
+    # the same codes under the other entry: a code names a kernel together with its entry (other loader, other instantiation)
+    (1, 4, 4, 64, 32, 1, 1, False, True, (6021, 6041, 424)), (2, 5, 7, 20, 40, 1, 1, False, True, (6031, 6021, 414)),
+    (1, 4, 4, 32, 16, 3, 1, False, True, (19014, 19024, 714)), (1, 4, 4, 128, 128, 1, 1, False, True, (6044, 6044, 444)),
+    (1, 4, 4, 64, 32, 3, 2, False, True, (19024, 19044, 724)), (68, 16, 16, 16, 16, 1, 1, False, True, (5164, 5164, 301)),
+    (32, 32, 40, 20, 40, 1, 1, False, True, (4364, 5264, 301)), (68, 16, 16, 32, 64, 1, 1, False, True, (4464, 5264, 302)),
+    (68, 5, 7, 100, 36, 3, 1, False, True, (19034, 17164, 714)), (17, 32, 32, 16, 32, 3, 1, False, True, (17248, 17148, 724)),
+    (1, 32, 64, 96, 512, 1, 1, False, True, (4448, 6034, 444)), (9, 2, 324, 192, 192, 1, 1, False, True, (3043, 3043, 434)),
+    (32, 32, 40, 20, 40, 3, 1, False, True, (17364, 17264, 714)), (1, 64, 64, 256, 32, 3, 1, False, True, (19024, 17448, 724)),
+    (17, 32, 32, 48, 48, 3, 1, False, False, (18348, 18348, 734)), (33, 2, 324, 48, 48, 3, 2, False, True, (19034, 17348, 734)),
+    (1, 64, 64, 256, 512, 1, 1, False, True, (3044, 3044, 444)),
+]
+STEM_ROUTE_CASES_16 = [
+    (2, 61, 92, 20, 16, 7, 4, 3, True, True, (64, 96), (611, 621)), (2, 61, 92, 20, 32, 7, 4, 3, True, True, (64, 96), (602, 622)),
+    (2, 61, 92, 20, 48, 7, 4, 3, True, True, (64, 96), (603, 623)), (2, 61, 92, 20, 64, 7, 4, 3, True, True, (64, 96), (614, 624)),
+    (2, 61, 92, 20, 48, 7, 4, 3, True, False, (64, 96), (39034, 834)), (2, 61, 92, 20, 48, 7, 4, 3, False, True, (64, 96), (49034, 934)),
+    (2, 61, 92, 20, 36, 7, 4, 3, False, True, (64, 96), (49034, 914)), (2, 61, 92, 8, 16, 5, 4, 2, True, True, (64, 96), (39014, 814)),
+    (4, 256, 256, 4, 48, 5, 4, 2, True, True, None, (38364, 834)), (4, 256, 256, 4, 48, 5, 4, 2, False, True, None, (48364, 934)),
+    (2, 61, 92, 24, 48, 7, 4, 3, True, True, (64, 96), (613, 834)),       # 24 channels: not the bf16 patch kernels' geometry
+]
+
+
+@pytest.mark.parametrize('case', CONV_ROUTE_CASES_16 + STEM_ROUTE_CASES_16, ids=lambda c: '-'.join(str(v) for v in c[-1]) + '@' + 'x'.join(str(v) for v in c[:5]))
+def test_conv_every_route_16bit(bf16_ops, case):
+    (tk.check_conv_routes if len(case) == 10 else tk.check_stem_routes)(bf16_ops, *case)
+
+
 @pytest.mark.parametrize('B,H,W,C,heads,part', [(3, 16, 20, 48, 2, (8, 10)), (2, 32, 40, 96, 4, (8, 10)), (1, 8, 10, 384, 16, (8, 10)),
                                                 # the other instantiations of the bf16-tile kernels: d = 32, one-head workgroups, padded
                                                 # partitions (60 of 64, 56 of 64 tokens), 240-token partitions of the 1 Mpx geometry

@@ -345,6 +345,108 @@ def test_conv_nhwc(ops, B, H, W, Cin, N, ks, stride):
     close(db, bias.grad, rtol=2e-4, atol=1e-4)
 
 
+def check_conv_routes(ops, B, H, W, Cin, N, ks, stride, bias, pack, want):
+    """One dense convolution on the routes ``want`` = (forward, dgrad, wgrad) of ``ops.conv_route``: forward with statistics, dgrad (write
+    and accumulate) and weight gradient against torch's conv2d and its autograd in fp64 on the CPU.  pack = False: the C calls are made
+    without a weight-pack buffer (the ops wrappers always offer one to the routes that read it)."""
+    pad = (ks - 1) // 2
+    got = (ops.conv_route(0, B, H, W, Cin, N, ks, stride, pad, ops.CF_COLSTATS | (ops.CF_PACK if pack else 0) | (ops.CF_BIAS if bias else 0)),
+           ops.conv_route(1, B, H, W, Cin, N, ks, stride, pad, ops.CF_PACK if pack else 0),
+           ops.conv_route(2, B, H, W, Cin, N, ks, stride, pad, ops.CF_WS | (ops.CF_DBIAS if bias else 0)))
+    assert got == tuple(want), 'the shape no longer reaches the routes this row is here for'
+    x = rnd((B, Cin, H, W), 1).double().requires_grad_(True)
+    w = rnd((N, Cin, ks, ks), 2, 0.1).double().requires_grad_(True)
+    b = rnd((N,), 3).double().requires_grad_(True) if bias else None
+    ref = F.conv2d(x, w, b, stride=stride, padding=pad)
+    dy = rnd(ref.shape, 4)
+    ref.backward(dy.double())
+    xn, dyn = x.detach().float().permute(0, 2, 3, 1).contiguous().to(DEV), dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    wd, bd = w.detach().float().to(DEV), (b.detach().float().to(DEV) if bias else None)
+    cs = torch.zeros((2, N), dtype=torch.float64, device=DEV)
+    acc = rnd(tuple(xn.shape), 9).to(DEV)
+    if pack:
+        y = ops.conv_nhwc_fwd(xn, wd, bd, stride=stride, colstats=cs)
+        dx = ops.conv_nhwc_dgrad(dyn, wd, xn.shape, stride=stride)
+        dx2 = ops.conv_nhwc_dgrad(dyn, wd, xn.shape, stride=stride, out=acc.clone(), accumulate=True)
+    else:
+        lib, p, st = ops._l(), ops._p, ops._stream()
+        y, dx, dx2 = torch.empty(tuple(ref.permute(0, 2, 3, 1).shape), device=DEV), torch.empty_like(xn), acc.clone()
+        assert lib.leod_conv_nhwc_fwd(p(xn), p(wd), p(bd), p(y), p(cs), 1, None, None, None, None, 1e-5, B, H, W, Cin, N, ks, stride, pad, None, 0, st) == 0
+        assert lib.leod_conv_nhwc_dgrad(p(dyn), p(wd), p(dx), 0, B, H, W, Cin, N, ks, stride, pad, None, 0, st) == 0
+        assert lib.leod_conv_nhwc_dgrad(p(dyn), p(wd), p(dx2), 1, B, H, W, Cin, N, ks, stride, pad, None, 0, st) == 0
+    refn = ref.detach().permute(0, 2, 3, 1)
+    close(y, refn, rtol=5e-5, atol=1e-5, fwd=True, what='fwd')
+    close(cs[0], refn.reshape(-1, N).sum(0), rtol=1e-5, atol=1e-4, what='colstats sum')
+    close(cs[1], (refn.reshape(-1, N) ** 2).sum(0), rtol=1e-5, atol=1e-4, what='colstats sumsq')
+    close(dx, x.grad.permute(0, 2, 3, 1), rtol=1e-4, atol=1e-5, what='dgrad')
+    close(dx2, x.grad.permute(0, 2, 3, 1) + acc.cpu(), rtol=1e-4, atol=1e-5, what='dgrad acc')
+    dw, db = torch.zeros_like(wd), (torch.zeros(N, device=DEV) if bias else None)
+    ops.conv_nhwc_wgrad(dyn, xn, dw, db, stride=stride)
+    close(dw, w.grad, rtol=2e-4, atol=1e-4, what='wgrad')
+    if bias:
+        close(db, b.grad, rtol=2e-4, atol=1e-4, what='dbias')
+
+
+def check_stem_routes(ops, B, H, W, Cin, N, ks, stride, pad, u8, aligned, padded, want):
+    """The stem convolution on the routes ``want`` = (forward, wgrad) against conv2d over the zero-padded frame in fp64 on the CPU."""
+    flags = (ops.CF_U8 if u8 else 0) | (ops.CF_ALIGN4 if aligned else 0)
+    Hp, Wp = padded if padded is not None else (H, W)
+    assert (ops.conv_route(3, B, H, W, Cin, N, ks, stride, pad, flags, padded), ops.conv_route(4, B, H, W, Cin, N, ks, stride, pad, flags, padded)) == tuple(want)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randint(0, 12, (B, Cin, H, W), generator=g, dtype=torch.uint8) if u8 else rnd((B, Cin, H, W), 5)
+    w = rnd((N, Cin, ks, ks), 2, 0.05).double().requires_grad_(True)
+    ref = F.conv2d(F.pad(x.double(), (0, Wp - W, 0, Hp - H)), w, None, stride=stride, padding=pad)
+    dy = rnd(ref.shape, 3)
+    ref.backward(dy.double())
+    buf = torch.empty(x.numel() * x.element_size() + 16, dtype=torch.uint8, device=DEV)
+    off = (-buf.data_ptr()) % 16 + (0 if aligned else 1)                    # a copy of x at an address that is / is not a multiple of 4
+    xd = buf[off:off + x.numel() * x.element_size()].view(x.dtype).view(x.shape).copy_(x)
+    assert (xd.data_ptr() % 4 == 0) == aligned
+    y = ops.stem_conv_fwd(xd, w.detach().float().to(DEV), (Hp, Wp), stride, pad)
+    close(y, ref.detach().permute(0, 2, 3, 1), rtol=5e-5, atol=1e-5, fwd=True, what='stem fwd')
+    dw = torch.zeros((N, Cin, ks, ks), device=DEV)
+    ops.stem_conv_wgrad(dy.permute(0, 2, 3, 1).contiguous().to(DEV), xd, dw, (Hp, Wp), stride, pad)
+    close(dw, w.grad, rtol=2e-4, atol=1e-4, what='stem wgrad')
+
+
+# every (entry, route) pair of ops.conv_route that launches in precision mode f32, at the smallest shape that reaches it (tests/test_bf16_gpu.py
+# has the pairs of the 16-bit modes; tests/test_conv_routes_cpu.py keeps both lists equal to the launching pairs of its table): (B, H, W, Cin, N, ks, stride, bias, pack offered, (forward, dgrad, wgrad) codes).  The LDS-staged GEMMs need 2048
+# rows and 256 workgroups, i.e. 8 k - 17 k pixels at these widths; the parity-class dgrad needs B (H/2) (W/2) % 16 == 0 (% 128 for its LDS form).
+CONV_ROUTE_CASES_F32 = [
+    (1, 4, 4, 16, 32, 1, 1, False, True, (6021, 6011, 424)), (1, 4, 4, 16, 32, 3, 1, True, True, (19024, 19014, 724)),
+    (1, 4, 4, 64, 128, 1, 1, False, True, (6041, 6044, 444)), (1, 4, 4, 192, 48, 3, 1, False, True, (19034, 19044, 734)),
+    (68, 5, 7, 36, 100, 1, 1, True, True, (5164, 6031, 414)), (3, 32, 40, 16, 160, 1, 1, False, True, (5264, 6014, 424)),
+    (17, 32, 32, 32, 64, 1, 1, False, True, (4464, 5264, 444)), (2, 64, 64, 48, 96, 1, 1, False, True, (4348, 6031, 434)),
+    (17, 32, 32, 16, 16, 3, 1, False, True, (17148, 17148, 714)), (9, 2, 324, 192, 48, 1, 1, False, True, (6034, 4448, 434)),
+    (17, 32, 32, 36, 100, 1, 1, False, True, (5164, 4364, 414)), (17, 32, 32, 32, 64, 3, 1, False, True, (17448, 17248, 744)),
+    (17, 32, 32, 64, 32, 3, 2, False, True, (19024, 27464, 724)), (2, 64, 64, 48, 96, 3, 1, False, True, (17348, 19034, 734)),
+    (33, 16, 20, 36, 100, 3, 2, False, True, (17164, 29034, 714)), (17, 32, 32, 48, 48, 3, 2, False, False, (19034, 28348, 734)),
+    (17, 32, 32, 48, 48, 3, 2, False, True, (19034, 27348, 734)), (17, 64, 64, 20, 32, 3, 2, False, True, (17264, 27264, 724)),
+    (17, 32, 32, 36, 100, 3, 1, False, True, (17164, 17364, 714)), (2, 64, 64, 192, 48, 3, 2, False, True, (19034, 27448, 734)),
+    (1, 8, 8, 48, 16, 3, 2, False, True, (19014, 29031, 714)), (2, 64, 64, 48, 96, 3, 1, False, False, (18348, 19034, 734)),
+    # the same codes under the other entry: a code names a kernel together with its entry (other loader, other instantiation)
+    (1, 4, 4, 32, 16, 1, 1, False, True, (6011, 6021, 414)), (1, 4, 4, 64, 32, 1, 1, False, True, (6021, 6041, 424)),
+    (1, 4, 4, 32, 64, 3, 2, False, True, (19044, 19024, 744)), (68, 5, 7, 100, 36, 1, 1, False, True, (6031, 5164, 414)),
+    (32, 32, 40, 20, 40, 1, 1, False, True, (4364, 5264, 414)), (68, 5, 7, 100, 36, 3, 1, False, True, (19034, 17164, 714)),
+    (2, 64, 64, 96, 192, 1, 1, False, True, (4448, 4348, 434)), (2, 32, 32, 512, 256, 1, 1, False, True, (6044, 4464, 444)),
+    (32, 32, 40, 20, 40, 3, 1, False, True, (17364, 17264, 714)), (17, 32, 32, 64, 32, 3, 1, False, True, (17248, 17448, 724)),
+    (17, 32, 32, 48, 48, 3, 1, False, True, (17348, 17348, 734)), (17, 32, 32, 48, 48, 3, 1, False, False, (18348, 18348, 734)),
+]
+# (B, H, W, Cin, N, ks, stride, pad, uint8, aligned, padded frame, (forward, wgrad) codes)
+STEM_ROUTE_CASES_F32 = [
+    (2, 61, 92, 20, 16, 7, 4, 3, True, True, (64, 96), (611, 631)), (2, 61, 92, 20, 32, 7, 4, 3, True, True, (64, 96), (612, 632)),
+    (2, 61, 92, 20, 48, 7, 4, 3, True, True, (64, 96), (613, 633)), (2, 61, 92, 20, 64, 7, 4, 3, True, True, (64, 96), (614, 634)),
+    (2, 61, 92, 20, 48, 7, 4, 3, True, False, (64, 96), (39034, 834)), (2, 61, 92, 20, 48, 7, 4, 3, False, True, (64, 96), (49034, 934)),
+    (2, 61, 92, 20, 36, 7, 4, 3, False, True, (64, 96), (49034, 914)), (2, 61, 92, 8, 16, 5, 4, 2, True, True, (64, 96), (39014, 814)),
+    (4, 256, 256, 4, 48, 5, 4, 2, True, True, None, (38364, 834)), (4, 256, 256, 4, 48, 5, 4, 2, False, True, None, (48364, 934)),
+]
+
+
+@pytest.mark.parametrize('case', CONV_ROUTE_CASES_F32 + STEM_ROUTE_CASES_F32, ids=lambda c: '-'.join(str(v) for v in c[-1]) + '@' + 'x'.join(str(v) for v in c[:5]))
+def test_conv_every_route(ops, case):
+    (check_conv_routes if len(case) == 10 else check_stem_routes)(ops, *case)
+
+
 @pytest.mark.parametrize('stat_rep', [1, 32])
 def test_conv_bn_eval_and_train(ops, stat_rep):
     B, H, W, Cin, N = 3, 8, 12, 32, 64

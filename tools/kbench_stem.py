@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """Stem convolution (7x7 / stride 4 over raw uint8 voxels) forward + weight gradient at the benchmarked shape (T*B = 168 frames of
-20 x 240 x 304, padded 256 x 320 -> 64 x 80 x 48), both precision modes.  usage: python tools/kbench_stem.py"""
+20 x 240 x 304, padded 256 x 320 -> 64 x 80 x 48: STEP_STEM of tests/test_conv_routes_cpu.py), both precision modes.  usage: python tools/kbench_stem.py"""
 import os, sys, time
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 import torch
 from leod_amd import ops
+from test_conv_routes_cpu import STEP_STEM
 
 dev = torch.device('cuda', 0)
-B, C, H, W, Hp, Wp, N = 168, 20, 240, 304, 256, 320, 48
+_, B, H, W, C, N, _, _, _, (Hp, Wp) = STEP_STEM
 g = torch.Generator().manual_seed(0)
 x = ((torch.rand((B, C, H, W), generator=g) < 0.08) * torch.randint(1, 10, (B, C, H, W), generator=g)).to(torch.uint8).to(dev)
 w = (torch.randn((N, C, 7, 7), generator=g) * 0.05).to(dev)
