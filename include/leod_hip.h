@@ -479,6 +479,17 @@ int leod_voxelize_u8(const long* x, const long* y, const long* pol, const long* 
  * +-count_cutoff (count_cutoff < 0 = none, <= 127).  counts_ws: bins*H*W int32 of scratch. */
 int leod_mixed_density_i8(const long* x, const long* y, const long* pol, const long* t, long n_events, int* counts_ws,
                           signed char* out, int bins, int H, int W, int count_cutoff, leod_stream_t stream);
+/* Recording ingestion (csrc/k_ingest.hip): the raw 8-byte records of a Prophesee .dat file (u32 t in microseconds; i32 with x in bits 0-13,
+ * y in bits 14-27, p in bit 28), time sorted, to the stacked histograms of n_win windows.  Window w holds events win_off[w] ..
+ * win_off[w+1]-1 (win_off: n_win + 1 ascending int64 offsets on the device); out[w] equals leod_voxelize_u8 on exactly those events
+ * (t0 / t1 = the window's first / last event time; an empty window is all zeros).  ds2 != 0 (H and W even) writes [.., H/2, W/2] =
+ * full[.., 1::2, 1::2] of the full-resolution histogram, what nearest-exact interpolation at scale 0.5 selects.  The windows are processed
+ * ws_windows at a time: one clear, one count launch, one finalise launch per chunk; counts_ws holds ws_windows * 2*bins*Ho*Wo int32
+ * (16-byte aligned for the packed finalise stores, else they go out byte-wise).  An event with x >= W or y >= H is skipped and added to *dropped (device counter the caller zeroes; may be NULL).
+ * count_cutoff <= 0: none. */
+int leod_voxelize_dat_windows(const void* records, long n_events, const long* win_off, int n_win, int* counts_ws, int ws_windows,
+                              unsigned char* out, int bins, int H, int W, int ds2, int count_cutoff, int fastmode, long* dropped,
+                              leod_stream_t stream);
 
 /* On-device spatial augmentation of uint8 event representations src/dst [T,B,C,H,W] (data/utils/augmentor.py:216-331,
  * 390-401): per batch sample b, params[b] = {hflip, mode (0 none, 1 zoom-in, 2 zoom-out), x0, y0, win_h, win_w, tflip}

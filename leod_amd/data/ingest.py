@@ -1,0 +1,187 @@
+"""Recording ingestion: a raw Prophesee recording (``*_td.dat`` events + ``*_bbox.npy`` boxes) to the dataset tree the loaders read
+(layout: ``leod_amd/data/utils/misc.py``).  The reference has no such stage (its docs/install.md points at pre-voxelised downloads).
+
+The record bytes go to the device as they lie in the file; ``ops.voxelize_dat_windows`` (csrc/k_ingest.hip) decodes them and writes
+the stacked histogram of every window.  The host only reads timestamps (sortedness, window offsets), moves bytes and writes labels.
+
+Window rule (the project's own), D = ``duration_us``:
+  * frame k holds the events with k*D < t <= (k+1)*D; events at t = 0 belong to frame 0; N = max(ceil(t_last / D), 1) frames;
+  * a box with timestamp t_l belongs to frame max(ceil(t_l / D) - 1, 0): a frame's labels sit at its end; boxes beyond frame N - 1 are
+    dropped; where boxes of several timestamps fall in one frame, those of the latest timestamp are kept.
+
+    python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4
+"""
+import argparse
+import glob
+import os
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from leod_amd.data.utils import dat_events
+from leod_amd.data.utils.types import DatasetType
+
+# labels.npz 'labels': the tree's 40-byte label record (data/genx_utils/labels.py reads it by field name)
+LABEL_DTYPE = np.dtype({'names': ['t', 'x', 'y', 'w', 'h', 'class_id', 'class_confidence', 'objectness'],
+                        'formats': ['<i8', '<f4', '<f4', '<f4', '<f4', '<u4', '<f4', '<f4'],
+                        'offsets': [0, 8, 12, 16, 20, 24, 28, 32], 'itemsize': 40})
+# older Prophesee annotation files name two fields differently (io/box_loading.py:27-44)
+_FIELD_ALIASES = {'ts': 't', 'confidence': 'class_confidence'}
+SENSOR_HW = {DatasetType.GEN1: (240, 304), DatasetType.GEN4: (720, 1280)}
+DEFAULT_KEEP_CLASSES = {DatasetType.GEN1: None, DatasetType.GEN4: (0, 1, 2)}        # the three classes the Gen4 configs train on
+FRAMES_PER_COPY = 32             # windows per device call and per copy through the pinned buffer
+
+
+def _dataset_type(dataset_type) -> DatasetType:
+    if isinstance(dataset_type, DatasetType):
+        return dataset_type
+    try:
+        return {'gen1': DatasetType.GEN1, 'gen4': DatasetType.GEN4}[str(dataset_type).lower()]
+    except KeyError:
+        raise ValueError(f'dataset type {dataset_type!r}: gen1 or gen4 expected') from None
+
+
+def ev_repr_name(duration_us: int, bins: int) -> str:
+    assert duration_us % 1000 == 0, 'the directory name states the window in whole milliseconds'
+    return f'stacked_histogram_dt={duration_us // 1000}_nbins={bins}'
+
+
+def label_frame(t_label, duration_us: int) -> np.ndarray:
+    """Frame of a box timestamp: max(ceil(t / D) - 1, 0)."""
+    t = np.asarray(t_label, dtype=np.int64)
+    return np.maximum(-(-t // int(duration_us)) - 1, 0)
+
+
+def convert_labels(boxes: np.ndarray, n_frames: int, duration_us: int, keep_classes: Optional[Sequence[int]] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Prophesee boxes (structured array) -> (labels [LABEL_DTYPE], objframe_idx_2_label_idx, objframe_idx_2_repr_idx) by the window rule.
+    Fields are copied by name, ``objectness`` = 1, ``track_id`` is dropped; no filtering but ``keep_classes`` (the evaluator applies the
+    Prophesee size and time filters itself)."""
+    names = {_FIELD_ALIASES.get(n, n): n for n in boxes.dtype.names}
+    missing = [n for n in LABEL_DTYPE.names if n != 'objectness' and n not in names]
+    if missing:
+        raise ValueError(f'box file lacks the fields {missing} (has {boxes.dtype.names})')
+    lab = np.zeros((len(boxes),), dtype=LABEL_DTYPE)
+    for n in LABEL_DTYPE.names:
+        if n != 'objectness':
+            lab[n] = boxes[names[n]]
+    lab['objectness'] = 1.0
+    if keep_classes is not None:
+        lab = lab[np.isin(lab['class_id'], np.asarray(list(keep_classes), dtype=np.int64))]
+    lab = lab[np.argsort(lab['t'], kind='stable')]
+    frame = label_frame(lab['t'], duration_us)
+    lab, frame = lab[frame < n_frames], frame[frame < n_frames]
+    # per frame only the boxes of its latest timestamp: after the stable sort these are the rows that equal the frame's last row in t
+    if len(lab):
+        last_row_of_frame = np.searchsorted(frame, frame, side='right') - 1
+        keep = lab['t'] == lab['t'][last_row_of_frame]
+        lab, frame = lab[keep], frame[keep]
+    repr_idx, starts = np.unique(frame, return_index=True)
+    return lab, starts.astype(np.int64), repr_idx.astype(np.int64)
+
+
+def voxelize_recording(records: np.ndarray, offsets: np.ndarray, frames_out: np.ndarray, bins: int, height: int, width: int, ds2: bool,
+                       device=None, frames_per_copy: int = FRAMES_PER_COPY) -> int:
+    """Memory-mapped records [n, 2] u32 + window offsets -> ``frames_out`` [N, 2*bins, Ho, Wo] uint8 (e.g. an ``open_memmap``),
+    ``frames_per_copy`` windows at a time through one pinned record buffer and one pinned frame buffer.  -> number of dropped events."""
+    import torch
+    from leod_amd import ops
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    n_frames = len(offsets) - 1
+    assert frames_out.shape[0] == n_frames and frames_out.dtype == np.uint8
+    spans = [(k, min(k + frames_per_copy, n_frames)) for k in range(0, n_frames, frames_per_copy)]
+    most = max([int(offsets[b] - offsets[a]) for a, b in spans] + [1])
+    rec_pin = torch.empty((most, 8), dtype=torch.uint8).pin_memory()
+    out_pin = torch.empty((min(frames_per_copy, n_frames),) + tuple(frames_out.shape[1:]), dtype=torch.uint8).pin_memory()
+    rec_np, out_np = rec_pin.numpy().view('<u4'), out_pin.numpy()
+    dropped = torch.zeros((1,), dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        for a, b in spans:
+            lo, hi = int(offsets[a]), int(offsets[b])
+            rec_np[:hi - lo] = records[lo:hi]
+            rec_dev = rec_pin[:hi - lo].to(device, non_blocking=True)
+            out, d = ops.voxelize_dat_windows(rec_dev, offsets[a:b + 1] - lo, bins, height, width, ds2=ds2)
+            dropped += d
+            out_pin[:b - a].copy_(out, non_blocking=True)
+            torch.cuda.current_stream().synchronize()           # the pinned buffers are reused by the next span
+            frames_out[a:b] = out_np[:b - a]
+    return int(dropped.item())
+
+
+def ingest_recording(dat_fn: str, bbox_fn: str, out_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
+                     keep_classes: Optional[Sequence[int]] = None, write: str = 'npy') -> Dict:
+    """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
+    ``event_representations_ds2_nearest.npy`` at half resolution for Gen4), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
+    ``keep_classes`` None: every class for Gen1, (0, 1, 2) for Gen4.  -> a small report."""
+    if write != 'npy':
+        raise ValueError(f"write={write!r}: only the raw 'npy' frame file is written (an HDF5 writer is not part of this package)")
+    dataset_type = _dataset_type(dataset_type)
+    ds2 = dataset_type == DatasetType.GEN4
+    hdr, records = dat_events.open_records(dat_fn)
+    height, width = SENSOR_HW[dataset_type]
+    for name, got, want in (('Height', hdr.height, height), ('Width', hdr.width, width)):
+        if got is not None and got != want:
+            raise ValueError(f'{dat_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
+    offsets = dat_events.scan_windows(records, duration_us, what=dat_fn)
+    n_frames = len(offsets) - 1
+    if keep_classes is None:
+        keep_classes = DEFAULT_KEEP_CLASSES[dataset_type]
+    labels, label_idx, repr_idx = convert_labels(np.load(bbox_fn), n_frames, duration_us, keep_classes)
+
+    ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
+    os.makedirs(ev_dir, exist_ok=True)
+    os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
+    frame_fn = os.path.join(ev_dir, 'event_representations' + ('_ds2_nearest' if ds2 else '') + '.npy')
+    shape = (n_frames, 2 * bins) + ((height // 2, width // 2) if ds2 else (height, width))
+    mm = np.lib.format.open_memmap(frame_fn + '.tmp', mode='w+', dtype=np.uint8, shape=shape)
+    try:
+        dropped = voxelize_recording(records, offsets, mm, bins, height, width, ds2)
+        mm.flush()
+    finally:
+        del mm
+    os.replace(frame_fn + '.tmp', frame_fn)
+    np.save(os.path.join(ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
+    np.savez(os.path.join(out_dir, 'labels_v2', 'labels.npz'), labels=labels, objframe_idx_2_label_idx=label_idx)
+    return dict(recording=out_dir, frames=n_frames, events=int(hdr.n_events), dropped_events=dropped, labelled_frames=int(len(repr_idx)),
+                boxes=int(len(labels)))
+
+
+def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
+                 keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False):
+    """Every ``<name>_td.dat`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  -> the reports, in name order."""
+    reports = []
+    for dat_fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat'))):
+        stem = os.path.basename(dat_fn)[:-len('_td.dat')]
+        bbox_fn = os.path.join(src_dir, stem + '_bbox.npy')
+        if not os.path.exists(bbox_fn):
+            raise FileNotFoundError(f'{dat_fn} has no box file {bbox_fn}')
+        rep = ingest_recording(dat_fn, bbox_fn, os.path.join(dst_dir, stem), dataset_type, duration_us=duration_us, bins=bins,
+                               keep_classes=keep_classes, write=write)
+        if verbose:
+            print(rep, flush=True)
+        reports.append(rep)
+    return reports
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog='python -m leod_amd.data.ingest', description=__doc__.split('\n\n')[0])
+    ap.add_argument('src', help="directory of *_td.dat + *_bbox.npy pairs, or one that holds such directories named train / val / test")
+    ap.add_argument('dst', help='dataset path to write (dst/<split>/<recording>/...)')
+    ap.add_argument('--dataset', required=True, choices=['gen1', 'gen4'])
+    ap.add_argument('--duration-us', type=int, default=50_000)
+    ap.add_argument('--bins', type=int, default=10)
+    ap.add_argument('--keep-classes', type=int, nargs='*', default=None)
+    args = ap.parse_args(argv)
+    splits = [s for s in ('train', 'val', 'test') if os.path.isdir(os.path.join(args.src, s))]
+    pairs = [(os.path.join(args.src, s), os.path.join(args.dst, s)) for s in splits] or [(args.src, args.dst)]
+    n = 0
+    for src, dst in pairs:
+        n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
+                              verbose=True))
+    if n == 0:
+        ap.error(f'no *_td.dat under {args.src}')
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

@@ -1530,6 +1530,49 @@ def voxelize_u8(x, y, pol, t, bins, height, width, count_cutoff=None, fastmode=T
     return out
 
 
+# int32 count workspace of one chunk of windows (voxelize_dat_windows): 32 Gen1 windows = 187 MB, the fastest of the sweep in DESIGN.md section 4
+# (the chunk's counts are cleared, counted into and read back while they still sit in the 256 MB Infinity Cache; 64 windows no longer do)
+INGEST_WS_BYTES = 32 * 2 * 10 * 240 * 304 * 4
+
+
+def ingest_ws_windows(bins, height, width, ds2=False) -> int:
+    """Default number of windows per chunk of ``voxelize_dat_windows``: as many as fit ``INGEST_WS_BYTES`` of int32 counts."""
+    per_win = 2 * bins * (height // 2 if ds2 else height) * (width // 2 if ds2 else width) * 4
+    return max(1, INGEST_WS_BYTES // per_win)
+
+
+def voxelize_dat_windows(records_u8, win_off, bins, height, width, ds2=False, count_cutoff=None, fastmode=True, ws_windows=None):
+    """Raw Prophesee .dat records on the device (uint8 [n_events * 8] or [n_events, 8], as they lie in the file, time sorted) ->
+    (out uint8 [n_win, 2*bins, Ho, Wo], dropped int64 [1]).  Window w holds events win_off[w] .. win_off[w+1]-1 (int64 [n_win + 1],
+    ascending, first >= 0, last <= n_events; a host tensor / array is checked and uploaded, a device tensor is taken as it is) and equals
+    ``voxelize_u8`` on those events; ``ds2`` keeps full[.., 1::2, 1::2].  ``dropped`` counts the events outside [0,W) x [0,H), which are
+    skipped.  3 * ceil(n_win / ws_windows) enqueues (``ws_windows`` None: ``ingest_ws_windows``)."""
+    _ck(records_u8, torch.uint8, 'records')
+    if records_u8.numel() % 8:
+        raise LeodHipError(f'records: {records_u8.numel()} bytes are no whole number of 8-byte events')
+    if ds2 and (height % 2 or width % 2):
+        raise LeodHipError(f'ds2 needs an even height and width, got {height} x {width}')
+    dev = records_u8.device
+    n_events = records_u8.numel() // 8
+    if not (isinstance(win_off, torch.Tensor) and win_off.is_cuda):
+        off = torch.as_tensor(win_off, dtype=torch.int64).reshape(-1)
+        if off.numel() < 1 or int(off[0]) < 0 or int(off[-1]) > n_events or bool((off[1:] < off[:-1]).any()):
+            raise LeodHipError('win_off: ascending offsets within [0, n_events] expected')
+        win_off = off.to(dev)
+    _ck(win_off, torch.int64, 'win_off')
+    n_win = win_off.numel() - 1
+    Ho, Wo = (height // 2, width // 2) if ds2 else (height, width)
+    ws_windows = ingest_ws_windows(bins, height, width, ds2) if ws_windows is None else int(ws_windows)
+    ws_windows = max(1, min(ws_windows, max(n_win, 1)))
+    ws = torch.empty((ws_windows * 2 * bins * Ho * Wo,), dtype=torch.int32, device=dev)
+    out = torch.empty((n_win, 2 * bins, Ho, Wo), dtype=torch.uint8, device=dev)
+    dropped = torch.zeros((1,), dtype=torch.int64, device=dev)
+    check(_l().leod_voxelize_dat_windows(_p(records_u8), n_events, _p(win_off), n_win, _p(ws), ws_windows, _p(out), bins, height, width,
+                                          1 if ds2 else 0, 0 if count_cutoff is None else int(count_cutoff), 1 if fastmode else 0,
+                                          _p(dropped), _stream()), 'voxelize_dat_windows')
+    return out, dropped
+
+
 def mixed_density_i8(x, y, pol, t, bins, height, width, count_cutoff=None):
     """MixedDensityEventStack.construct (data/utils/representations.py:132-221): int64 events sorted in time -> int8 [bins, H, W]."""
     for a in (x, y, pol, t):
