@@ -70,6 +70,17 @@ int leod_partition_attn_16bit_ok(int B, int H, int W, int C, int heads, int ph, 
  * (maxvit.py:185-270 under train.py:236-243). */
 int leod_partition_attn_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw);
 int leod_attn_block_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw);
+/* Which kernels leod_partition_attn_fwd (entry 0) / leod_partition_attn_bwd (entry 1) run for this geometry in the current precision mode
+ * -- a query: nothing is launched, no memory is read.  The calls themselves switch on the same value, so the two cannot differ.
+ * flags, what the call is told about its tensors: 1 qkv rows are 16-bit (bit 0 of qkv_bf16), 2 O (forward) / dO (backward) rows are 16-bit
+ * (bit 1 of qkv_bf16), 4 dqkv is written as bf16 (dqkv_bf16; backward only).  Code = 10000 F + 100 PT + D, PT = ceil(ph pw / 16):
+ *   F = 1   register-direct fp32 kernels, one launch forward, q pass then kv pass backward; D = 16 ceil(d / 16)
+ *   F = 2   LDS kernels on fp32 tiles; D = d (24 | 32)
+ *   F = 3   LDS kernels on 16-bit tiles; D = d (24 | 32)
+ *   0       no partitions: nothing to launch;    -1 / -3: what the call returns for these arguments (NULL pointers apart)
+ * The bf16 / fp16 operand format inside a family follows from the precision mode and is not part of the code.
+ * leod_partition_attn_16bit_ok / _o16_ok are derivations: forward and backward with the 16-bit flags both route to F = 3. */
+int leod_partition_attn_route(int entry, int B, int H, int W, int C, int heads, int ph, int pw, int flags);
 int leod_linear_lsres_bf16_fwd(const void* a16, const float* W, const float* bias, const float* gamma, const float* res, float* out,
                                int M, int N, int K, leod_stream_t stream);
 /* out16[M,N] = bf16(LN(x) W^T + bias), stats_out [M,2]; -3 unless the row-streaming kernel covers (M, N, K) in precision mode bf16. */
@@ -131,7 +142,7 @@ int leod_convlstm_gates_bwd(const float* dh, const float* dh2, const float* dc_n
  * slots 1..T are written; gates_out [T,M,4,C] optional -- without it (inference: no backward pass will read the history) only slot T of cbuf
  * is written. */
 int leod_convlstm_seq_mode(int C);
-/* mode 3 (C = 256 / 384 in precision mode bf16: the weight slice of a wave does not fit its registers): like mode 2, and the waves
+/* mode 3 (C = 192 / 256 / 384 / 512 in the 16-bit precision modes: the weight slice of a wave does not fit its registers): like mode 2, and the waves
  * stream their MFMA B fragments from a fragment-ordered bf16 copy of W_h -- leod_convlstm_seq_pack writes it (once per step, shared by
  * forward and backward) into a buffer of leod_convlstm_seq_pack_bytes(C) bytes, passed as wpack (NULL in modes 1 / 2). */
 long leod_convlstm_seq_pack_bytes(int C);
@@ -148,6 +159,18 @@ int leod_convlstm_seq_bwd(const float* dh_seq, const float* dc_last, const float
  * the sequence kernels' own lane-linear layout (T x ceil(M / 16) * 16 x 4C halfs, written and read by these two calls only), dgates_out to
  * bf16 rows [T][M][4C] -- the reference's autocast holds the gates in 16 bits as well (rnn.py:58-62 under train.py:236-243). */
 int leod_convlstm_seq_gates16_ok(int C);
+/* Which kernel leod_convlstm_seq_fwd (entry 0) / leod_convlstm_seq_bwd (entry 1) run for this channel count in the current precision
+ * mode -- a query: nothing is launched, no memory is read.  The calls themselves switch on the same value.
+ * flags, what the call is given: 1 xin is the hoisted projection (x_is_projection), 2 gates16, 4 a wpack.
+ *   forward    1000 + C   fused [x | h] contraction, weights resident in registers
+ *              2000 + C   hoisted projection, weights resident in registers
+ *              3000 + C   hoisted projection, weights streamed from the pack
+ *   backward   3000 + C   streamed from the pack
+ *              4000 + C   weights resident in registers
+ *   -1 / -3: what the call returns for these arguments (NULL pointers and M, T <= 0 apart); -3 from the backward (precision mode f32 at
+ *   C = 192 among others) tells the caller to run the per-timestep kernels.
+ * leod_convlstm_seq_mode, leod_convlstm_seq_gates16_ok, leod_convlstm_seq_pack_bytes and the check of leod_convlstm_seq_pack are derivations. */
+int leod_convlstm_seq_route(int entry, int C, int flags);
 
 /* dy_fmt 1 (here and in leod_linear_wgrad; dy_bf16 of leod_linear_dgrad_lnbwd): dy points to bf16 elements -- in precision mode bf16 the
  * wide gradients du (out_bf16 of leod_linear_dgrad_gelu16) and dqkv are stored as the bf16 their consumers feed to the MFMAs anyway.

@@ -11,7 +11,7 @@
 // *transposed* (S^T = K Q^T, keys along MFMA rows) so that the softmax'ed accumulator registers are
 // already laid out as the A operand of the P.V MFMA (k index = lane>>4): no LDS, no shuffles apart
 // from the 2-step cross-row-group reductions.  P = 80 tokens -> 5 key tiles, 20 accumulator VGPRs.
-#include "common.hpp"
+#include "attn_route.hpp"
 #include <type_traits>
 
 struct AttnGeom {
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
 //   A/B fragments along the head dim : one ds_read_b128 per lane (row stride == 4 mod 16 floats: conflict-free),
 //   B fragments along the token dim  : ds_read_b32 (key rows 4q+r land in distinct 16-bank groups).
 // The register-direct kernels above re-read K/V of a partition from global memory in every one of its PT waves and in
-// operand layout (16 rows x 64 B per instruction, 4-byte V loads); they stay as the LEOD_ATTN_LDS=0 reference.
+// operand layout (16 rows x 64 B per instruction, 4-byte V loads); they serve the head dimensions other than 24 and 32.
 // Outputs go back through LDS so that a wave instruction stores whole per-token segments (O: d floats per head,
 // dqkv: the full 3d*HG segment with dq, dk, dv of both passes of the fused backward).
 // =====================================================================================================================
@@ -1017,113 +1017,101 @@ __global__ __launch_bounds__(64 * PT * HG) void attn_bwd_lds16_kernel(const void
     }
 }
 
-template <int PT, int D, int HG>
-static int run_attn_lds(int which, const float* qkv, const float* dout, float* out, float* lse, float* dqkv,
-                        const AttnGeom& g, float scale, hipStream_t s) {
-    const int NP = g.B * (g.H / g.ph) * (g.W / g.pw);
-    const int nblk = NP * (g.heads / HG);
-    if (nblk == 0) return LEOD_OK;
+// what the entry points hand to the launchers
+struct AttnArgs { const float* qkv; const float* dout; float* out; float* lse; float* dsum; float* dqkv; };
+
+// the LDS kernels: one workgroup of PT waves per (partition, head); t16 = the 16-bit-tile family (route F = 3)
+template <int PT, int D>
+static int launch_attn_lds(int entry, bool t16, const AttnArgs& a, const AttnGeom& g, float scale, hipStream_t s) {
+    // heads per workgroup: the kernels keep the parameter and are instantiated at 1 only (two heads never ran: see attn_route); written
+    // without it they compile to different code, if only by a few scalar instructions
+    constexpr int HG = 1;
+    const dim3 grid(g.B * (g.H / g.ph) * (g.W / g.pw) * (g.heads / HG)), blk(64 * PT * HG);
     const int TOK = 16 * PT, S = HG * 3 * D + 4, Sd = HG * D + 4;
-    // precision mode bf16 with bf16 qkv rows (and bf16 dqkv): the bf16-tile kernels
     const bool h16 = leod_precision_mode() == 2;               // 16-bit qkv / O rows are fp16
-    if (leod_precision() == 1 && which == 0 && (g.fmt & 1)) {
+    if (t16 && entry == AE_FWD) {
         const size_t lds = ((size_t)TOK * A16L<D, HG>::SD + 8) * 4 + (size_t)PT * HG * 16 * (D + 4) * 4;
-        if (h16) hipLaunchKernelGGL((attn_fwd_lds16_kernel<PT, D, HG, 2>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, out, lse, g, scale);
-        else hipLaunchKernelGGL((attn_fwd_lds16_kernel<PT, D, HG, 1>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, out, lse, g, scale);
-        return leod_launch_status();
-    }
-    if (leod_precision() == 1 && which == 1 && (g.fmt & 3) == 3) {
+        if (h16) hipLaunchKernelGGL((attn_fwd_lds16_kernel<PT, D, HG, 2>), grid, blk, lds, s, a.qkv, a.out, a.lse, g, scale);
+        else hipLaunchKernelGGL((attn_fwd_lds16_kernel<PT, D, HG, 1>), grid, blk, lds, s, a.qkv, a.out, a.lse, g, scale);
+    } else if (t16) {
         const size_t lds = ((size_t)TOK * (A16L<D, HG>::SD + A16L<D, HG>::SDD) + 16) * 4;
-        if (h16) hipLaunchKernelGGL((attn_bwd_lds16_kernel<PT, D, HG, true>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, dout, lse, dqkv, g, scale);
-        else hipLaunchKernelGGL((attn_bwd_lds16_kernel<PT, D, HG, false>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, dout, lse, dqkv, g, scale);
-        return leod_launch_status();
-    }
-    if ((g.fmt & 12) || (g.fmt && h16)) return LEOD_ERR_UNSUPPORTED;   // 16-bit O / dO rows, fp16 rows: the 16-bit-tile kernels only
-    if (which == 0) {
+        if (h16) hipLaunchKernelGGL((attn_bwd_lds16_kernel<PT, D, HG, true>), grid, blk, lds, s, a.qkv, a.dout, a.lse, a.dqkv, g, scale);
+        else hipLaunchKernelGGL((attn_bwd_lds16_kernel<PT, D, HG, false>), grid, blk, lds, s, a.qkv, a.dout, a.lse, a.dqkv, g, scale);
+    } else if (entry == AE_FWD) {
         const size_t lds = (size_t)TOK * S * sizeof(float);
-        LEOD_BY_OPFMT(hipLaunchKernelGGL((attn_fwd_lds_kernel<PT, D, HG, OF>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, out, lse, g, scale));
+        LEOD_BY_OPFMT(hipLaunchKernelGGL((attn_fwd_lds_kernel<PT, D, HG, OF>), grid, blk, lds, s, a.qkv, a.out, a.lse, g, scale));
     } else {
         const size_t lds = (size_t)TOK * (S + Sd) * sizeof(float);
-        if (leod_precision() == 1) hipLaunchKernelGGL((attn_bwd_lds_kernel<PT, D, HG, true>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, dout, lse, dqkv, g, scale);
-        else hipLaunchKernelGGL((attn_bwd_lds_kernel<PT, D, HG>), dim3(nblk), dim3(64 * PT * HG), lds, s, qkv, dout, lse, dqkv, g, scale);
+        if (leod_precision() == 1) hipLaunchKernelGGL((attn_bwd_lds_kernel<PT, D, HG, true>), grid, blk, lds, s, a.qkv, a.dout, a.lse, a.dqkv, g, scale);
+        else hipLaunchKernelGGL((attn_bwd_lds_kernel<PT, D, HG>), grid, blk, lds, s, a.qkv, a.dout, a.lse, a.dqkv, g, scale);
     }
     return leod_launch_status();
 }
 
-// ---------------------------------------------------------------------------------------------------
+// the register-direct kernels: one wave per (partition, head, 16-token tile); the backward is a q pass, then a kv pass
 template <int PT, int DCH>
-static int run_attn(int which, const float* qkv, const float* dout, float* out, float* lse, float* dsum, float* dqkv,
-                    const AttnGeom& g, float scale, hipStream_t s) {
-    const int NP = g.B * (g.H / g.ph) * (g.W / g.pw);
-    const int ntasks = NP * g.heads * PT;
-    if (ntasks == 0) return LEOD_OK;
+static int launch_attn_reg(int entry, const AttnArgs& a, const AttnGeom& g, float scale, hipStream_t s) {
+    const int ntasks = g.B * (g.H / g.ph) * (g.W / g.pw) * g.heads * PT;
     const dim3 grid(cdiv(ntasks, 4)), blk(256);
-    if (which == 0) hipLaunchKernelGGL((attn_fwd_kernel<PT, DCH>), grid, blk, 0, s, qkv, out, lse, g, scale, ntasks);
-    else if (which == 1) hipLaunchKernelGGL((attn_bwd_q_kernel<PT, DCH>), grid, blk, 0, s, qkv, dout, lse, dqkv, dsum, g, scale, ntasks);
-    else hipLaunchKernelGGL((attn_bwd_kv_kernel<PT, DCH>), grid, blk, 0, s, qkv, dout, lse, dsum, dqkv, g, scale, ntasks);
+    if (entry == AE_FWD) {
+        hipLaunchKernelGGL((attn_fwd_kernel<PT, DCH>), grid, blk, 0, s, a.qkv, a.out, a.lse, g, scale, ntasks);
+        return leod_launch_status();
+    }
+    hipLaunchKernelGGL((attn_bwd_q_kernel<PT, DCH>), grid, blk, 0, s, a.qkv, a.dout, a.lse, a.dqkv, a.dsum, g, scale, ntasks);
+    if (const int rc = leod_launch_status(); rc != LEOD_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<PT, DCH>), grid, blk, 0, s, a.qkv, a.dout, a.lse, a.dsum, a.dqkv, g, scale, ntasks);
     return leod_launch_status();
 }
 
-static int dispatch_attn(int which, const float* qkv, const float* dout, float* out, float* lse, float* dsum,
-                         float* dqkv, const AttnGeom& g, hipStream_t s) {
-    if (g.C != g.heads * g.d || (g.d & 3) || g.d > 32 || g.H % g.ph || g.W % g.pw) return LEOD_ERR_ARG;
-    const int P = g.ph * g.pw, PT = (P + 15) / 16, DCH = (g.d + 15) / 16;
+// The only switch that launches: every template argument comes from the route code (10000 F + 100 PT + D, attn_route.hpp).
+static int launch_attn(int route, int entry, const AttnArgs& a, const AttnGeom& g, hipStream_t s) {
+    if (route <= 0) return route;
     const float scale = 1.0f / sqrtf((float)g.d);
-    constexpr int use_lds = 1;
-    // One head per workgroup (5 waves for an 80-token partition) instead of two (10 waves, the CU's wave limit at three workgroups): six
-    // workgroups per CU overlap their load / MFMA / store phases better -- backward 984 -> 889 us per step over the four stages, forward of
-    // stage 1 126 -> 116 us, the rest equal (tools/kbench.py attn, profiles/r04_z_attn_hg_kbench.txt).  (hg1: bit 0 forward, bit 1 backward.)
-    static const int hg1 = 3;
-    const int HG = (g.heads % 2 == 0 && 2 * PT <= 16 && !((hg1 & 1) && which == 0) && !((hg1 & 2) && which != 0)) ? 2 : 1;
-    static const int force_pad1 = 1;
-    // (round 1 routed one-head workgroups with padded partitions to the register-direct
-    // backward; the defect behind it was a mis-merged ds_write2_b32 in the <4, 32, 1> instantiation, see the kernel's epilogue)
-    const bool lds_shape = (g.d == 24 || g.d == 32) && (PT <= 5 || PT == 8 || (HG == 1 && (PT == 10 || PT == 15))) &&
-                           !(HG == 1 && P < 16 * PT && which != 0 && !force_pad1);
-    if (use_lds && lds_shape) {
-        // which: 0 forward, 1 fused backward (the register-direct path runs 1 = q pass, then 2 = kv pass)
-        if (which == 2) return LEOD_OK;                       // the fused LDS backward already produced dK / dV
-#define ATTL(PTV, DV, HGV) if (PT == PTV && g.d == DV && HG == HGV) return run_attn_lds<PTV, DV, HGV>(which, qkv, dout, out, lse, dqkv, g, scale, s);
-#define ATTD(PTV, HGV) ATTL(PTV, 24, HGV) ATTL(PTV, 32, HGV)
-        ATTD(1, 1) ATTD(1, 2) ATTD(2, 1) ATTD(2, 2) ATTD(3, 1) ATTD(3, 2) ATTD(4, 1) ATTD(4, 2) ATTD(5, 1) ATTD(5, 2)
-        ATTD(8, 1) ATTD(8, 2) ATTD(10, 1) ATTD(15, 1)
-#undef ATTD
-#undef ATTL
-        return LEOD_ERR_UNSUPPORTED;
-    }
-    if (g.fmt) return LEOD_ERR_UNSUPPORTED;                    // the register-direct kernels read / write fp32 only
-#define ATT(PTV, DV) if (PT == PTV && DCH == DV) return run_attn<PTV, DV>(which, qkv, dout, out, lse, dsum, dqkv, g, scale, s);
-    ATT(1, 1) ATT(1, 2) ATT(4, 1) ATT(4, 2) ATT(5, 1) ATT(5, 2) ATT(15, 2) ATT(2, 1) ATT(2, 2) ATT(3, 2) ATT(8, 2) ATT(10, 2)
+    const int F = route / 10000;
+    if (F == 1) switch (route % 10000) {
+#define ATT(PT, DCH) case 100 * PT + 16 * DCH: return launch_attn_reg<PT, DCH>(entry, a, g, scale, s);
+        ATT(1, 1) ATT(2, 1) ATT(4, 1) ATT(5, 1) ATT(1, 2) ATT(2, 2) ATT(3, 2) ATT(4, 2) ATT(5, 2) ATT(8, 2) ATT(10, 2) ATT(15, 2)
 #undef ATT
+    } else switch (route % 10000) {
+#define ATTL(PT) case 100 * PT + 24: return launch_attn_lds<PT, 24>(entry, F == 3, a, g, scale, s); \
+                 case 100 * PT + 32: return launch_attn_lds<PT, 32>(entry, F == 3, a, g, scale, s);
+        ATTL(1) ATTL(2) ATTL(3) ATTL(4) ATTL(5) ATTL(8) ATTL(10) ATTL(15)
+#undef ATTL
+    }
     return LEOD_ERR_UNSUPPORTED;
 }
 
-// out[M,C] = softmax(q k^T / sqrt(d)) v per partition/head ; lse[M,heads] (optional) = log-sum-exp of the scaled scores
-// 1: forward and fused backward of this geometry run on the LDS kernels in the current precision mode bf16, i.e. qkv may be handed
-// over as bf16 (qkv_bf16) and dqkv produced as bf16 (dqkv_bf16); 0: fp32 tensors only
-LEOD_API int leod_partition_attn_16bit_ok(int B, int H, int W, int C, int heads, int ph, int pw) {
-    if (leod_precision() != 1 || heads <= 0 || C % heads || H % ph || W % pw) return 0;
-    constexpr int use_lds = 1;
-    static const int on = 1;
-    const int d = C / heads, P = ph * pw, PT = (P + 15) / 16;
-    const int HG = (heads % 2 == 0 && 2 * PT <= 16) ? 2 : 1;
-    const bool inst = PT <= 5 || PT == 8 || (HG == 1 && (PT == 10 || PT == 15));
-    static const int force_pad1 = 1;
-    return on && use_lds && (d == 24 || d == 32) && inst && !(HG == 1 && P < 16 * PT && !force_pad1);
-}
-// 1: on top of leod_partition_attn_16bit_ok, the attention output O may be written as bf16 (forward, bit 1 of qkv_bf16) and its gradient
-// dO read as bf16 (backward, bit 1 of qkv_bf16): the bf16-tile kernels stage both as the bf16 MFMA operands they are anyway
-LEOD_API int leod_partition_attn_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw) {
-    static const int on = 1;
-    return on && leod_partition_attn_16bit_ok(B, H, W, C, heads, ph, pw);
+// Which kernel family leod_partition_attn_fwd (entry 0) / _bwd (entry 1) run for this geometry in the current precision mode, or the
+// error they return: the entries switch on the same value.  Codes and flags: include/leod_hip.h.
+LEOD_API int leod_partition_attn_route(int entry, int B, int H, int W, int C, int heads, int ph, int pw, int flags) {
+    return attn_route(entry, B, H, W, C, heads, ph, pw, flags);
 }
 
+// 1: forward and fused backward of this geometry run on the 16-bit-tile kernels in the current precision mode, i.e. qkv may be handed
+// over as 16-bit rows (qkv_bf16) and dqkv produced as bf16 (dqkv_bf16); 0: fp32 tensors only
+static bool attn_both_lds16(int B, int H, int W, int C, int heads, int ph, int pw, int o16) {
+    return attn_route(AE_FWD, B, H, W, C, heads, ph, pw, AF_QKV16 | o16, true) / 10000 == 3 &&
+           attn_route(AE_BWD, B, H, W, C, heads, ph, pw, AF_QKV16 | o16 | AF_DQKV16, true) / 10000 == 3;
+}
+LEOD_API int leod_partition_attn_16bit_ok(int B, int H, int W, int C, int heads, int ph, int pw) { return attn_both_lds16(B, H, W, C, heads, ph, pw, 0); }
+// 1: on top of leod_partition_attn_16bit_ok, the attention output O may be written as 16-bit rows (forward, bit 1 of qkv_bf16) and its
+// gradient dO read as bf16 (backward, bit 1 of qkv_bf16): the 16-bit-tile kernels stage both as the 16-bit MFMA operands they are anyway
+LEOD_API int leod_partition_attn_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw) { return attn_both_lds16(B, H, W, C, heads, ph, pw, AF_O16); }
+
+// AttnGeom of a call: fmt as the kernels read it -- bit 0 qkv rows 16-bit, bit 1 dqkv written as bf16, bit 2 O rows 16-bit, bit 3 dO rows bf16
+static AttnGeom attn_geom(int entry, int B, int H, int W, int C, int heads, int ph, int pw, int window, int flags) {
+    const int fmt = ((flags & AF_QKV16) ? 1 : 0) | (entry == AE_BWD && (flags & AF_DQKV16) ? 2 : 0) | ((flags & AF_O16) ? (entry == AE_FWD ? 4 : 8) : 0);
+    return AttnGeom{B, H, W, C, heads, C / heads, ph, pw, window, fmt};
+}
+
+// out[M,C] = softmax(q k^T / sqrt(d)) v per partition/head ; lse[M,heads] (optional) = log-sum-exp of the scaled scores
 LEOD_API int leod_partition_attn_fwd(const float* qkv, float* out, float* lse, int B, int H, int W, int C, int heads,
                                      int ph, int pw, int window, int qkv_bf16, hipStream_t stream) {
     LeodFwdScope fwd_scope;
     if (!qkv || !out || heads <= 0) return LEOD_ERR_ARG;
-    AttnGeom g{B, H, W, C, heads, C / heads, ph, pw, window, ((qkv_bf16 & 1) ? 1 : 0) | ((qkv_bf16 & 2) ? 4 : 0)};
-    return dispatch_attn(0, qkv, nullptr, out, lse, nullptr, nullptr, g, stream);
+    const int flags = qkv_bf16 & (AF_QKV16 | AF_O16);
+    return launch_attn(attn_route(AE_FWD, B, H, W, C, heads, ph, pw, flags), AE_FWD, AttnArgs{qkv, nullptr, out, lse, nullptr, nullptr},
+                       attn_geom(AE_FWD, B, H, W, C, heads, ph, pw, window, flags), stream);
 }
 
 // dqkv[M,3C] = gradient of the attention core wrt the qkv rows; dsum [M,heads] is scratch
@@ -1131,8 +1119,8 @@ LEOD_API int leod_partition_attn_bwd(const float* qkv, const float* dout, const 
                                      int B, int H, int W, int C, int heads, int ph, int pw, int window,
                                      int qkv_bf16, int dqkv_bf16, hipStream_t stream) {
     if (!qkv || !dout || !lse || !dsum || !dqkv || heads <= 0) return LEOD_ERR_ARG;
-    AttnGeom g{B, H, W, C, heads, C / heads, ph, pw, window, ((qkv_bf16 & 1) ? 1 : 0) | (dqkv_bf16 ? 2 : 0) | ((qkv_bf16 & 2) ? 8 : 0)};
-    int rc = dispatch_attn(1, qkv, dout, nullptr, const_cast<float*>(lse), dsum, dqkv, g, stream);
-    if (rc != LEOD_OK) return rc;
-    return dispatch_attn(2, qkv, dout, nullptr, const_cast<float*>(lse), dsum, dqkv, g, stream);
+    const int flags = (qkv_bf16 & (AF_QKV16 | AF_O16)) | (dqkv_bf16 ? AF_DQKV16 : 0);
+    return launch_attn(attn_route(AE_BWD, B, H, W, C, heads, ph, pw, flags), AE_BWD,
+                       AttnArgs{qkv, dout, nullptr, const_cast<float*>(lse), dsum, dqkv},
+                       attn_geom(AE_BWD, B, H, W, C, heads, ph, pw, window, flags), stream);
 }

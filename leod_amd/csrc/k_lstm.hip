@@ -19,7 +19,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "common.hpp"
+#include "lstm_route.hpp"
 
 template <bool FAST> __device__ __forceinline__ float tanh_(float x) {
     if constexpr (FAST) return 2.0f * sigmoidf_(2.0f * x) - 1.0f;         // v_exp / v_rcp: |error| ~1e-7, bf16 mode only
@@ -561,49 +561,87 @@ __global__ __launch_bounds__(C * 2) void lstm_seq_bwd_stream_kernel(const float*
             }
 }
 
-// registers of the resident B fragments per lane: 4 gates x K/16 chunks x (2 | 4) dwords
-static inline int fwd_bregs(int K, bool bf) { return 4 * (K / 16) * (bf ? 2 : 4); }
+struct LstmSeqFwdArgs { const float* xin; float* hbuf; float* cbuf; const float* W; const float* bias; float* gates_out; const void* wpack;
+                        int M, T, zero_state, gates16; };
+struct LstmSeqBwdArgs { const float* dh_seq; const float* dc_last; const float* gates; const float* cbuf; const float* W; float* dgates_out;
+                        float* dh0; float* dc0; const void* wpack; int M, T, zero_state, gates16; };
+
+// The launches of one table row (lstm_route.hpp): FAM = the row's family in the format BF (false: precision mode f32), so that a row
+// instantiates the kernels its routes name and no others.
+template <int C, int FAM, bool BF>
+static int launch_lstm_seq_fwd(const LstmSeqFwdArgs& a, hipStream_t s) {
+    const dim3 grid(cdiv(a.M, 16));
+    if constexpr (FAM == 3) {
+        const s8v* wpf = reinterpret_cast<const s8v*>(a.wpack);
+        LEOD_BY_OPFMT16({
+            if (a.gates16) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<C, true, OF>), grid, dim3(C * 2), 0, s, a.xin, a.hbuf, a.cbuf, wpf, a.gates_out, a.M, a.T, a.zero_state);
+            else hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<C, false, OF>), grid, dim3(C * 2), 0, s, a.xin, a.hbuf, a.cbuf, wpf, a.gates_out, a.M, a.T, a.zero_state);
+        });
+    } else if constexpr (FAM != 0 && BF) {
+        LEOD_BY_OPFMT16({
+            if (a.gates16) hipLaunchKernelGGL((lstm_seq_fwd_kernel<C, FAM == 1, OF, true>), grid, dim3(C * 4), 0, s, a.xin, a.hbuf, a.cbuf, a.W, a.bias, a.gates_out, a.M, a.T, a.zero_state);
+            else hipLaunchKernelGGL((lstm_seq_fwd_kernel<C, FAM == 1, OF>), grid, dim3(C * 4), 0, s, a.xin, a.hbuf, a.cbuf, a.W, a.bias, a.gates_out, a.M, a.T, a.zero_state);
+        });
+    } else if constexpr (FAM != 0) {
+        hipLaunchKernelGGL((lstm_seq_fwd_kernel<C, FAM == 1, 0>), grid, dim3(C * 4), 0, s, a.xin, a.hbuf, a.cbuf, a.W, a.bias, a.gates_out, a.M, a.T, a.zero_state);
+    } else {
+        return LEOD_ERR_UNSUPPORTED;
+    }
+    return leod_launch_status();
+}
+template <int C, int FAM, bool BF>
+static int launch_lstm_seq_bwd(const LstmSeqBwdArgs& a, hipStream_t s) {
+    const dim3 grid(cdiv(a.M, 16));
+    if constexpr (FAM == 3) {
+        const s8v* wpb = reinterpret_cast<const s8v*>(a.wpack) + (long)C * C / 2;
+        if (a.gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<C, true>), grid, dim3(C * 2), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, wpb, a.dgates_out, a.dh0, a.dc0, a.M, a.T);
+        else hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<C>), grid, dim3(C * 2), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, wpb, a.dgates_out, a.dh0, a.dc0, a.M, a.T);
+    } else if constexpr (FAM != 0) {
+        if (BF && a.gates16) hipLaunchKernelGGL((lstm_seq_bwd_kernel<C, BF, BF>), grid, dim3(C * 4), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, a.W, a.dgates_out, a.dh0, a.dc0, a.M, a.T, a.zero_state);
+        else hipLaunchKernelGGL((lstm_seq_bwd_kernel<C, BF>), grid, dim3(C * 4), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, a.W, a.dgates_out, a.dh0, a.dc0, a.M, a.T, a.zero_state);
+    } else {
+        return LEOD_ERR_UNSUPPORTED;
+    }
+    return leod_launch_status();
+}
+// The launch switch: the route's C picks the table row, the precision mode its column (the route's family is that column's entry).
+#define LSTM_LAUNCH_ROW(CV, F32, B16) case CV: return bf ? LSTM_LAUNCH<CV, B16, true>(a, s) : LSTM_LAUNCH<CV, F32, false>(a, s);
+static int launch_lstm_seq(int route, const LstmSeqFwdArgs& a, hipStream_t s) {
+    if (route <= 0) return route;
+    const bool bf = leod_precision() == 1;
+#define LSTM_LAUNCH launch_lstm_seq_fwd
+    switch (route % 1000) { LSTM_SEQ_TABLE(LSTM_LAUNCH_ROW) }
+#undef LSTM_LAUNCH
+    return LEOD_ERR_UNSUPPORTED;
+}
+static int launch_lstm_seq(int route, const LstmSeqBwdArgs& a, hipStream_t s) {
+    if (route <= 0) return route;
+    const bool bf = leod_precision() == 1;
+#define LSTM_LAUNCH launch_lstm_seq_bwd
+    switch (route % 1000) { LSTM_SEQ_TABLE(LSTM_LAUNCH_ROW) }
+#undef LSTM_LAUNCH
+    return LEOD_ERR_UNSUPPORTED;
+}
+#undef LSTM_LAUNCH_ROW
+
+// Which sequence kernel leod_convlstm_seq_fwd (entry 0) / _bwd (entry 1) run for this channel count in the current precision mode, or
+// the error they return: the entries switch on the same value.  Codes and flags: include/leod_hip.h.
+LEOD_API int leod_convlstm_seq_route(int entry, int C, int flags) { return lstm_seq_route(entry, C, flags); }
 
 /* 1 = fused [x | h] contraction, 2 = hoisted x projection (xin = gx), 3 = hoisted + streamed weights (wpack from leod_convlstm_seq_pack),
  * 0 = sequence kernel not available for this C / precision */
-LEOD_API int leod_convlstm_seq_mode(int C) {
-    const bool bf = leod_precision() == 1;
-    static const int stream_on = 1;
-    if (bf && stream_on && (C == 256 || C == 384 || C == 512)) return 3;               // hoisted x projection + weights streamed from a packed bf16 copy
-    // C = 192: the register-resident kernels spill (96 weight registers of the 168 a wave gets at 12 waves per workgroup: 79 / 83 spilled
-    // VGPRs, tools/kernel_regs.py) -- streamed fragments (295 KB per timestep and workgroup from L2) are the faster of the two
-    static const int stream192 = 1;
-    if (bf && stream_on && stream192 && C == 192) return 3;
-    if (C != 32 && C != 48 && C != 64 && C != 96 && C != 128 && C != 192) return 0;
-    if (fwd_bregs(2 * C, bf) <= 96) return 1;                               // beyond ~100 resident registers the kernels spill
-    if (fwd_bregs(C, bf) <= (C >= 192 ? 96 : 128)) return 2;
-    return 0;
-}
-
-#define LSTM_FWD_CASE(CV, FXV)                                                                                                  \
-    if (C == CV && fx == FXV) {                                                                                                 \
-        if (bf && gates16) { LEOD_BY_OPFMT16(hipLaunchKernelGGL((lstm_seq_fwd_kernel<CV, FXV, OF, true>), grid, dim3(CV * 4), 0, stream, xin, hbuf, cbuf, W, bias, gates_out, M, T, zero_state)); } \
-        else if (bf) { LEOD_BY_OPFMT16(hipLaunchKernelGGL((lstm_seq_fwd_kernel<CV, FXV, OF>), grid, dim3(CV * 4), 0, stream, xin, hbuf, cbuf, W, bias, gates_out, M, T, zero_state)); } \
-        else hipLaunchKernelGGL((lstm_seq_fwd_kernel<CV, FXV, 0>), grid, dim3(CV * 4), 0, stream, xin, hbuf, cbuf, W, bias, gates_out, M, T, zero_state);  \
-        return leod_launch_status();                                                                                            \
-    }
+LEOD_API int leod_convlstm_seq_mode(int C) { return lstm_seq_mode(C); }
 
 // 1: the sequence kernels of this channel count keep the gates as fp16 (opaque layout, T x ceil(M / 16) * 16 x 4C halfs) and write the
 // gate gradients as bf16 rows [T][M][4C] when asked to (gates16 of leod_convlstm_seq_fwd / _bwd); 0: fp32 tensors only
-LEOD_API int leod_convlstm_seq_gates16_ok(int C) {
-    static const int on = 1;
-    if (!on || leod_precision() != 1) return 0;
-    const int mode = leod_convlstm_seq_mode(C);
-    if (mode == 3) return 1;
-    return mode != 0 && (4 * C / 16) * 2 <= (C >= 192 ? 96 : 128);         // the backward sequence kernel must exist as well
-}
+LEOD_API int leod_convlstm_seq_gates16_ok(int C) { return lstm_seq_route(LE_BWD, C, LF_GATES16 | LF_PACK) > 0; }
 
-// bytes of the packed bf16 weight copy mode 3 needs (0 otherwise)
-LEOD_API long leod_convlstm_seq_pack_bytes(int C) { return leod_convlstm_seq_mode(C) == 3 ? (long)2 * 4 * C * C * 2 : 0; }
+// bytes of the packed 16-bit weight copy the streamed routes need (0 otherwise)
+LEOD_API long leod_convlstm_seq_pack_bytes(int C) { return lstm_seq_route(LE_BWD, C, LF_PACK) / 1000 == 3 ? (long)2 * 4 * C * C * 2 : 0; }
 
-// wpack <- the two fragment-ordered bf16 copies of W_h (once per step: forward and backward of the same weights share it)
+// wpack <- the two fragment-ordered 16-bit copies of W_h (once per step: forward and backward of the same weights share it)
 LEOD_API int leod_convlstm_seq_pack(const float* W, void* wpack, int C, hipStream_t stream) {
-    if (!W || !wpack || leod_convlstm_seq_mode(C) != 3) return LEOD_ERR_ARG;
+    if (!W || !wpack || leod_convlstm_seq_pack_bytes(C) == 0) return LEOD_ERR_ARG;
     s8v* wpf = reinterpret_cast<s8v*>(wpack);                    // C * C / 2 sixteen-byte fragments each for the forward and the backward copy
     hipLaunchKernelGGL(lstm_pack_kernel, dim3(cdiv((long)C * C, 256)), dim3(256), 0, stream, W, wpf, wpf + (long)C * C / 2, C,
                        leod_precision_mode() == 2 ? 1 : 0);
@@ -613,64 +651,15 @@ LEOD_API int leod_convlstm_seq_pack(const float* W, void* wpack, int C, hipStrea
 LEOD_API int leod_convlstm_seq_fwd(const float* xin, int x_is_projection, float* hbuf, float* cbuf, const float* W, const float* bias,
                                    float* gates_out, const void* wpack, int M, int C, int T, int zero_state, int gates16, hipStream_t stream) {
     LeodFwdScope fwd_scope;
-    if (gates16 && !leod_convlstm_seq_gates16_ok(C)) return LEOD_ERR_ARG;
+    const int route = lstm_seq_route(LE_FWD, C, (x_is_projection ? LF_PROJECTION : 0) | (gates16 ? LF_GATES16 : 0) | (wpack ? LF_PACK : 0));
     if (!xin || !hbuf || !cbuf || !W || !bias || M <= 0 || T <= 0 || (long)M * 4 * C >= (1L << 31)) return LEOD_ERR_ARG;
-    const int mode = leod_convlstm_seq_mode(C);
-    if (mode == 0 || (mode == 1) != (x_is_projection == 0)) return LEOD_ERR_UNSUPPORTED;
-    if (mode == 3) {
-        if (!wpack) return LEOD_ERR_ARG;
-        const s8v* wpf = reinterpret_cast<const s8v*>(wpack);
-        const dim3 g3(cdiv(M, 16));
-        LEOD_BY_OPFMT16({
-            if (C == 512 && gates16) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<512, true, OF>), g3, dim3(1024), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else if (C == 512) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<512, false, OF>), g3, dim3(1024), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else if (C == 384 && gates16) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<384, true, OF>), g3, dim3(768), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else if (C == 384) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<384, false, OF>), g3, dim3(768), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else if (C == 192 && gates16) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<192, true, OF>), g3, dim3(384), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else if (C == 192) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<192, false, OF>), g3, dim3(384), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else if (gates16) hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<256, true, OF>), g3, dim3(512), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-            else hipLaunchKernelGGL((lstm_seq_fwd_stream_kernel<256, false, OF>), g3, dim3(512), 0, stream, xin, hbuf, cbuf, wpf, gates_out, M, T, zero_state);
-        });
-        return leod_launch_status();
-    }
-    const bool bf = leod_precision() == 1, fx = mode == 1;
-    const dim3 grid(cdiv(M, 16));
-    LSTM_FWD_CASE(32, true) LSTM_FWD_CASE(48, true) LSTM_FWD_CASE(64, true) LSTM_FWD_CASE(96, true)
-    LSTM_FWD_CASE(64, false) LSTM_FWD_CASE(96, false) LSTM_FWD_CASE(128, false) LSTM_FWD_CASE(192, false)
-    return LEOD_ERR_UNSUPPORTED;
+    return launch_lstm_seq(route, LstmSeqFwdArgs{xin, hbuf, cbuf, W, bias, gates_out, wpack, M, T, zero_state, gates16}, stream);
 }
-
-#define LSTM_BWD_CASE(CV)                                                                                                       \
-    if (C == CV) {                                                                                                              \
-        if (bf && gates16) hipLaunchKernelGGL((lstm_seq_bwd_kernel<CV, true, true>), grid, dim3(CV * 4), 0, stream, dh_seq, dc_last, gates, cbuf, W, dgates_out, dh0, dc0, M, T, zero_state); \
-        else if (bf) hipLaunchKernelGGL((lstm_seq_bwd_kernel<CV, true>), grid, dim3(CV * 4), 0, stream, dh_seq, dc_last, gates, cbuf, W, dgates_out, dh0, dc0, M, T, zero_state); \
-        else hipLaunchKernelGGL((lstm_seq_bwd_kernel<CV, false>), grid, dim3(CV * 4), 0, stream, dh_seq, dc_last, gates, cbuf, W, dgates_out, dh0, dc0, M, T, zero_state);  \
-        return leod_launch_status();                                                                                            \
-    }
 
 LEOD_API int leod_convlstm_seq_bwd(const float* dh_seq, const float* dc_last, const float* gates, const float* cbuf, const float* W,
                                    float* dgates_out, float* dh0, float* dc0, const void* wpack, int M, int C, int T, int zero_state,
                                    int gates16, hipStream_t stream) {
-    if (gates16 && !leod_convlstm_seq_gates16_ok(C)) return LEOD_ERR_ARG;
     if (!gates || !cbuf || !W || !dgates_out || M <= 0 || T <= 0 || (long)M * 4 * C >= (1L << 31)) return LEOD_ERR_ARG;
-    const bool bf = leod_precision() == 1;
-    if (leod_convlstm_seq_mode(C) == 3) {
-        if (!wpack) return LEOD_ERR_ARG;
-        const s8v* wpb = reinterpret_cast<const s8v*>(wpack) + (long)C * C / 2;
-        const dim3 g3(cdiv(M, 16));
-        if (C == 512 && gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<512, true>), g3, dim3(1024), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else if (C == 512) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<512>), g3, dim3(1024), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else if (C == 384 && gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<384, true>), g3, dim3(768), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else if (C == 384) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<384>), g3, dim3(768), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else if (C == 192 && gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<192, true>), g3, dim3(384), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else if (C == 192) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<192>), g3, dim3(384), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else if (gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<256, true>), g3, dim3(512), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        else hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<256>), g3, dim3(512), 0, stream, dh_seq, dc_last, gates, cbuf, wpb, dgates_out, dh0, dc0, M, T);
-        return leod_launch_status();
-    }
-    // B fragments of the backward pass: 4C/16 chunks x (2 | 4) dwords
-    if ((4 * C / 16) * (bf ? 2 : 4) > (C >= 192 ? 96 : 128)) return LEOD_ERR_UNSUPPORTED;
-    const dim3 grid(cdiv(M, 16));
-    LSTM_BWD_CASE(32) LSTM_BWD_CASE(48) LSTM_BWD_CASE(64) LSTM_BWD_CASE(96) LSTM_BWD_CASE(128) LSTM_BWD_CASE(192)
-    return LEOD_ERR_UNSUPPORTED;
+    return launch_lstm_seq(lstm_seq_route(LE_BWD, C, (gates16 ? LF_GATES16 : 0) | (wpack ? LF_PACK : 0)),
+                           LstmSeqBwdArgs{dh_seq, dc_last, gates, cbuf, W, dgates_out, dh0, dc0, wpack, M, T, zero_state, gates16}, stream);
 }

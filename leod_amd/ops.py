@@ -291,6 +291,13 @@ def partition_attn_16bit_ok(B, H, W, C, heads, part) -> bool:
     return BF16_GRADS and bool(_l().leod_partition_attn_16bit_ok(B, H, W, C, heads, part[0], part[1]))
 
 
+def partition_attn_route(entry, B, H, W, C, heads, part, flags=0) -> int:
+    """The kernels ``partition_attn_fwd`` (entry 0) / ``partition_attn_bwd`` (entry 1) run for this geometry in the current precision mode, or
+    the negative error code they return (``leod_partition_attn_route`` in include/leod_hip.h lists the flags and the codes; nothing is launched).
+    flags: 1 qkv is 16-bit, 2 out / dout is 16-bit, 4 dqkv comes back as bfloat16.  A query for tests and tools, not for the step path."""
+    return int(_l().leod_partition_attn_route(entry, B, H, W, C, heads, part[0], part[1], flags))
+
+
 def partition_attn_bwd(qkv, dout, lse, heads, part, window):
     q16 = _is16(qkv)
     _ck(qkv, act16_dtype() if q16 else F32, 'qkv')
@@ -335,8 +342,16 @@ def convlstm_gates_bwd(dh, dc_next, gates, c_prev, c_t, want_dc_prev=True, dh2=N
 
 def convlstm_seq_mode(C: int) -> int:
     """0: no sequence kernel for this channel count / precision mode; 1: fused [x | h] contraction (xin = x_seq);
-    2: the caller supplies the time-batched projection gx = x W_x^T + b (leod_convlstm_seq_mode)."""
+    2: the caller supplies the time-batched projection gx = x W_x^T + b; 3: as 2, and the kernels stream their weights from the
+    ``convlstm_seq_pack`` buffer (leod_convlstm_seq_mode)."""
     return int(_l().leod_convlstm_seq_mode(int(C)))
+
+
+def convlstm_seq_route(entry, C: int, flags=0) -> int:
+    """The kernel ``convlstm_seq_fwd`` (entry 0) / ``convlstm_seq_bwd`` (entry 1) run for this channel count in the current precision mode, or
+    the negative error code they return (``leod_convlstm_seq_route`` in include/leod_hip.h lists the codes; nothing is launched).
+    flags: 1 xin is the hoisted projection, 2 fp16 gates, 4 a wpack is given.  A query for tests and tools, not for the step path."""
+    return int(_l().leod_convlstm_seq_route(entry, int(C), flags))
 
 
 def convlstm_seq_pack(W, C: int):

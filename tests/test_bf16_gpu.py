@@ -344,6 +344,17 @@ def test_partition_attn_bf16_tensors(bf16_ops, B, H, W, C, heads, part, window):
     tk.close(dq2.float(), qkv2.grad, what='bf16 dqkv from bf16 dO')
 
 
+# every (entry, route) pair of ops.partition_attn_route that launches in the 16-bit modes (rows as in test_kernels_gpu.ATTN_ROUTE_CASES_F32):
+# the register-direct and the fp32-tile kernels on fp32 tensors, the 16-bit-tile kernels on 16-bit qkv / bf16 dqkv (and 16-bit O / dO)
+ATTN_ROUTE_CASES_16 = tk.ATTN_ROUTE_CASES_F32 + [(part, d, True, (30000 + 100 * PT + d,) * 2)
+                                                 for d in (24, 32) for PT, parts in tk.ATTN_ROUTE_PARTS.items() for part in parts]
+
+
+@pytest.mark.parametrize('case', ATTN_ROUTE_CASES_16, ids=tk._attn_case_id)
+def test_attn_every_route_16bit(bf16_ops, case):
+    tk.check_attn_routes(bf16_ops, *case)
+
+
 @pytest.mark.parametrize('B,H,W,C,heads', [(21, 32, 40, 48, 2), (8, 32, 40, 96, 4), (28, 16, 20, 192, 8)])
 def test_attention_block_keeps_o_and_do_as_bf16(bf16_ops, B, H, W, C, heads):
     """Where leod_attn_block_o16_ok holds, the other consumers of O / dO take bf16 rows: proj + LayerScale + residual from bf16 O, the
@@ -516,6 +527,23 @@ def test_wgrad_wide_bf16(bf16_ops, M, N, K, dy16, xmode):
                                              (4, 2, 6, 10, 512, True), (11, 1, 5, 7, 512, False)])  # RVT-B stage 4: 16 waves per workgroup
 def test_convlstm_sequence_bf16(bf16_ops, T, B, H, W, C, state):
     tk.test_convlstm_sequence(bf16_ops, T, B, H, W, C, state)
+
+
+# every (entry, route) pair of ops.convlstm_seq_route that launches in the 16-bit modes: (C, (forward code, backward code))
+LSTM_SEQ_ROUTE_CASES_16 = [(32, (1032, 4032)), (48, (1048, 4048)), (64, (1064, 4064)), (96, (1096, 4096)), (128, (2128, 4128)),
+                           (192, (3192, 3192)), (256, (3256, 3256)), (384, (3384, 3384)), (512, (3512, 3512))]
+
+
+@pytest.mark.parametrize('g16', [True, False])
+@pytest.mark.parametrize('state', [True, False])
+@pytest.mark.parametrize('case', LSTM_SEQ_ROUTE_CASES_16, ids=lambda c: f'{c[1][0]}-{c[1][1]}')
+def test_convlstm_seq_every_route_16bit(bf16_ops, monkeypatch, case, state, g16):
+    """g16: fp16 gates and bf16 gate gradients, as the autograd function asks for them wherever leod_convlstm_seq_gates16_ok says so;
+    without: the same kernels' fp32-gate instantiations, which the function reaches when told that the answer is no."""
+    assert bf16_ops.convlstm_gates16_ok(case[0])
+    if not g16:
+        monkeypatch.setattr(bf16_ops, 'convlstm_gates16_ok', lambda C: False)
+    tk.check_lstm_seq_routes(bf16_ops, *case, state, g16)
 
 
 def test_full_size_training_step_bf16_vs_f32():

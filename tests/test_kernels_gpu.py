@@ -153,6 +153,56 @@ def test_partition_attn(ops, B, H, W, C, heads, part, window):
     close(dq, qkv.grad, rtol=5e-5, atol=5e-6, what='attn bwd')
 
 
+# Every (entry, route) pair of ops.partition_attn_route that launches, at the smallest shape that still exercises the indexing: one image
+# of 2 x 2 partitions (window and grid addressing differ: both run), two heads (the second checks the head offset), C = 2 d.  One
+# partition that fills its 16-token tiles and one padded one per tile count PT.  ((ph, pw), d, 16-bit tensors, (forward code, backward code))
+ATTN_ROUTE_PARTS = {1: ((4, 4), (3, 5)), 2: ((4, 8), (5, 6)), 3: ((6, 8), (5, 7)), 4: ((8, 8), (7, 8)), 5: ((8, 10), (7, 11)),
+                    8: ((8, 16), (11, 11)), 10: ((10, 16), (12, 13)), 15: ((12, 20), (15, 15))}
+ATTN_ROUTE_CASES_REG = [(part, d, False, (10000 + 100 * PT + D,) * 2)          # register-direct: d = 12 / 20 leave the last 16-wide chunk ragged
+                        for d, D, PTs in ((12, 16, (1, 2, 4, 5)), (20, 32, (1, 2, 3, 4, 5, 8, 10, 15))) for PT in PTs for part in ATTN_ROUTE_PARTS[PT]]
+ATTN_ROUTE_CASES_LDS32 = [(part, d, False, (20000 + 100 * PT + d,) * 2) for d in (24, 32) for PT, parts in ATTN_ROUTE_PARTS.items() for part in parts]
+ATTN_ROUTE_CASES_F32 = ATTN_ROUTE_CASES_REG + ATTN_ROUTE_CASES_LDS32
+
+
+def check_attn_routes(ops, part, d, t16, want):
+    """The routes are the ones the case is there for; then forward and backward against the fp32 CPU attention, window and grid.  t16: qkv
+    handed over as 16-bit rows and dqkv taken back as bf16, then O written / dO read as 16-bit rows as well (the same routes)."""
+    B, H, W, heads, C = 1, 2 * part[0], 2 * part[1], 2, 2 * d
+    for flags in (((1, 1 | 4), (1 | 2, 1 | 2 | 4)) if t16 else ((0, 0),)):
+        assert tuple(ops.partition_attn_route(e, B, H, W, C, heads, part, flags[e]) for e in (0, 1)) == tuple(want)
+    assert ops.partition_attn_16bit_ok(B, H, W, C, heads, part) == (want[0] // 10000 == 3 or (MODE['bf16'] and want[0] // 10000 == 2))
+    a16 = ops.act16_dtype()
+    for window in (True, False):
+        q0 = rnd((B, H, W, 3 * C), 7)
+        qkv = (q0.to(a16).float() if t16 else q0).requires_grad_(True)
+        ref = _attn_ref(qkv, heads, part, window)
+        dout = rnd(ref.shape, 8)
+        ref.backward(dout)
+        q = (q0.to(a16) if t16 else q0).to(DEV)
+        out, lse = ops.partition_attn_fwd(q, heads, part, window, want_lse=True)
+        close(out, ref, what=f'attn fwd {want[0]}', fwd=True)
+        dq = ops.partition_attn_bwd(q, dout.to(DEV), lse, heads, part, window)
+        assert dq.dtype is (torch.bfloat16 if t16 else torch.float32)
+        tol = {} if t16 else dict(rtol=5e-5, atol=5e-6)            # as test_partition_attn / test_partition_attn_bf16_tensors
+        close(dq.float(), qkv.grad, what=f'attn bwd {want[1]}', **tol)
+        if t16:
+            o16, lse2 = ops.partition_attn_fwd(q, heads, part, window, want_lse=True, out_bf16=True)
+            assert o16.dtype is a16 and torch.equal(lse2, lse) and torch.equal(o16, out.to(a16))
+            do16 = dout.to(torch.bfloat16)
+            qkv2 = qkv.detach().clone().requires_grad_(True)
+            _attn_ref(qkv2, heads, part, window).backward(do16.float())
+            close(ops.partition_attn_bwd(q, do16.to(DEV), lse, heads, part, window).float(), qkv2.grad, what='bf16 dqkv from bf16 dO')
+
+
+def _attn_case_id(c):
+    return f'{c[3][0]}-{c[3][1]}@{c[0][0]}x{c[0][1]}'
+
+
+@pytest.mark.parametrize('case', ATTN_ROUTE_CASES_F32, ids=_attn_case_id)
+def test_attn_every_route(ops, case):
+    check_attn_routes(ops, *case)
+
+
 @pytest.mark.parametrize('M,C,state', [(160, 32, True), (160, 32, False), (70, 48, True), (640, 384, True),
                                        (40960, 48, True), (10240, 96, False), (9000, 192, True)])
 def test_convlstm(ops, M, C, state):
@@ -229,6 +279,25 @@ def test_convlstm_sequence(ops, T, B, H, W, C, state):
     else:
         close(mod.conv1x1.weight.grad[:, :C], Wr.grad[:, :C], rtol=2e-4, atol=2e-5, what='dW_x')
     close(mod.conv1x1.bias.grad, br.grad, rtol=2e-4, atol=2e-5, what='db')
+
+
+# Every (entry, route) pair of ops.convlstm_seq_route that launches in precision mode f32: (C, (forward code, backward code))
+LSTM_SEQ_ROUTE_CASES_F32 = [(32, (1032, 4032)), (48, (1048, 4048)), (64, (2064, 4064)), (96, (2096, 4096)), (128, (2128, 4128))]
+
+
+def check_lstm_seq_routes(ops, C, want, state, g16=False):
+    """The routes are the ones the case is there for; then the sequence of test_convlstm_sequence at T = 3 on 35 rows (a ragged third
+    16-row tile)."""
+    fl = (1 if want[0] >= 2000 else 0) | (4 if want[0] >= 3000 else 0) | (2 if g16 else 0)
+    assert (ops.convlstm_seq_route(0, C, fl), ops.convlstm_seq_route(1, C, fl & ~1)) == tuple(want)
+    assert ops.convlstm_seq_mode(C) == want[0] // 1000
+    test_convlstm_sequence(ops, 3, 1, 5, 7, C, state)
+
+
+@pytest.mark.parametrize('state', [True, False])
+@pytest.mark.parametrize('case', LSTM_SEQ_ROUTE_CASES_F32, ids=lambda c: f'{c[1][0]}-{c[1][1]}')
+def test_convlstm_seq_every_route(ops, case, state):
+    check_lstm_seq_routes(ops, *case, state)
 
 
 @pytest.mark.parametrize('M,N,K', [(300, 144, 48), (1000, 48, 192), (257, 64, 32), (5000, 96, 96), (100, 1536, 384),
