@@ -530,6 +530,26 @@ int leod_augment_u8(const unsigned char* src, unsigned char* dst, const int* par
 int leod_augment_rot_u8(const unsigned char* src, unsigned char* dst, const int* params, const float* rot, int T, int B, int C,
                         int H, int W, leod_stream_t stream);
 
+/* Prediction-video frames (csrc/k_render.hip; reference vis_pred.py:74-93 for the base image, :126-215 for what is drawn on it): the
+ * event representation ev [L,C2,H,W] (uint8, or fp32 when ev_is_f32 != 0; counts >= 0, C2 = 2*bins) -> out [L, up*H, up*W, 3] uint8
+ * RGB rows, up = 1 or 2.  A source pixel with any channel > 0 is 0.25, every other 1.0; bilinear x2 (align_corners=False), * 255, rounded
+ * -- evaluated in integers: K = sum of the quarter weights wy*wx over the event taps, byte = (16320 - 765 K + 32) >> 6 (up = 1: 64 / 255).
+ * Overlay items, drawn in the same pass in item order (the later item wins): items [n_items,8] int32 = {frame, kind, x, y, a, b, c, rgb}
+ * sorted by frame, rgb = r | g<<8 | b<<16, coordinates in output pixels; frame_off [L+1] int32 = first item of every frame.
+ * kind 0: rectangle outline, corners (x,y)-(a,b), thickness 1 <= c <= 65536 (pixels in [x-c/2, a+(c-1)/2] x [y-c/2, b+(c-1)/2] that are not in
+ * [x+(c-1)/2+1, a-c/2-1] x [y+(c-1)/2+1, b-c/2-1]).  kind 1: one text line with bottom-left (x,y), integer scale 1 <= a <= 65536, bytes
+ * text[b .. b+c-1] in the 5 x 7 font of leod_render_font (advance 6a; a byte outside 0x20-0x7E is a solid block).  Everything is clipped
+ * to the frame.  ws: L*H*W bytes of scratch (the event mask).  n_items == 0: frame_off / items / text may be NULL.
+ * An item whose thickness / scale lies outside [1, 65536] or whose kind is neither 0 nor 1 draws nothing; a text byte whose offset lies
+ * outside [0, n_text) draws as a solid block (ops.render_frames refuses all of these before the upload).
+ * Returns 0; -1 for up not in {1,2}, an odd C2, non-positive L / C2 / H / W, negative n_items / n_text, NULL ev / out / ws, or n_items > 0
+ * with NULL frame_off / items; -3 for up*H or up*W above 32767; -2 if a launch failed. */
+int leod_render_frames_u8(const void* ev, int ev_is_f32, unsigned char* out, int L, int C2, int H, int W, int up, const int* frame_off,
+                          const int* items, int n_items, const unsigned char* text, int n_text, unsigned char* ws, leod_stream_t stream);
+/* The renderer's font, copied to HOST memory dst[95*7]: glyphs of ASCII 0x20-0x7E, 7 rows each from the top, one byte per row, bit 4 =
+ * leftmost of the 5 columns. */
+int leod_render_font(unsigned char* dst);
+
 /* dgrad of a Linear fused with the LayerNorm backward of its producer (x -> norm -> Linear, maxvit.py:267-269,110-118):
  * dx[M,K] = LN-backward(dy[M,N] @ W[N,K]) (+ dres), dgamma[K] += sum dn*xhat, dbeta[K] += sum dn, with x[M,K] the LayerNorm
  * input and stats[M,2] its saved (mean, rstd).  Stage-1 shapes only (K = 48, N = 144 / 192, M >= 16384): returns -3

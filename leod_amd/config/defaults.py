@@ -117,3 +117,12 @@ def full_config(dataset: str = 'gen1', size: str = 'small', model: str = 'rnndet
     if overrides:
         _deep_update(cfg, overrides)
     return create(cfg)
+
+
+def vis_config(dataset: str = 'gen1', size: str = 'small', model: str = 'rnndet', overrides: Optional[Mapping] = None):
+    """Equivalent of ``vis_pred.py model=<model> dataset=<dataset> +experiment/<dataset>=<size>.yaml`` (config/vis.yaml): inference only, one
+    recording per batch, no test-time augmentation, ``num_video`` recordings, ``reverse`` = a second pass over the time-reversed events."""
+    cfg = dict(num_video=5, reverse=False, batch_size=dict(eval=1), hardware=dict(num_workers=dict(eval=1)), tta=dict(enable=False))
+    if overrides:
+        _deep_update(cfg, overrides)
+    return full_config(dataset, size, model=model, is_train=False, overrides=cfg)

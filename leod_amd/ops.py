@@ -1602,6 +1602,103 @@ def mixed_density_i8(x, y, pol, t, bins, height, width, count_cutoff=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# prediction-video frames (csrc/k_render.hip)
+# ---------------------------------------------------------------------------------------------------
+RENDER_RECT, RENDER_TEXT = 0, 1
+RENDER_MAX_SCALE = 65536                                     # text scale / rectangle thickness: the limit include/leod_hip.h states (beyond it the kernel draws nothing)
+
+
+def render_font():
+    """The renderer's 5 x 7 font as the library holds it: uint8 numpy array [95, 7], glyphs of ASCII 0x20-0x7E, rows from the top, bit 4 =
+    leftmost column."""
+    import numpy as np
+    buf = (ctypes.c_ubyte * (95 * 7))()
+    check(_l().leod_render_font(buf), 'render_font')
+    return np.frombuffer(bytes(buf), dtype=np.uint8).reshape(95, 7).copy()
+
+
+def _render_items(L, frame_off, items, text):
+    """Host-side check of the overlay arrays of ``render_frames`` -> (frame_off int32 [L+1], items int32 [n,8], text uint8 [m]) as numpy
+    arrays, or (None, None, None) without items.  ValueError on anything the kernel would have to index blindly."""
+    import numpy as np
+    if items is None or len(items) == 0:
+        if frame_off is not None:
+            fo = np.asarray(frame_off, dtype=np.int64).reshape(-1)
+            if fo.size and (fo[0] != 0 or fo[-1] != 0 or (np.diff(fo) < 0).any()):
+                raise ValueError('render_frames: frame_off names items, but there are none')
+        return None, None, None
+    it = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items, dtype=np.int64)
+    if it.ndim != 2 or it.shape[1] != 8:
+        raise ValueError(f'render_frames: items must be [n_items, 8], got {it.shape}')
+    if frame_off is None:
+        raise ValueError('render_frames: items without frame_off')
+    fo = np.asarray(frame_off.cpu() if isinstance(frame_off, torch.Tensor) else frame_off, dtype=np.int64).reshape(-1)
+    if fo.size != L + 1:
+        raise ValueError(f'render_frames: frame_off must have L + 1 = {L + 1} entries, got {fo.size}')
+    if fo[0] != 0:
+        raise ValueError(f'render_frames: frame_off[0] must be 0, got {fo[0]}')
+    if (np.diff(fo) < 0).any():
+        raise ValueError('render_frames: frame_off must be ascending')
+    if fo[-1] != len(it):
+        raise ValueError(f'render_frames: frame_off[-1] = {fo[-1]} but there are {len(it)} items')
+    if np.abs(it).max() >= 2 ** 31:
+        raise ValueError('render_frames: an item field does not fit int32')
+    if text is None:
+        tx = np.zeros((0,), dtype=np.uint8)
+    elif isinstance(text, (bytes, bytearray)):
+        tx = np.frombuffer(bytes(text), dtype=np.uint8)
+    else:
+        tx = np.asarray(text.cpu() if isinstance(text, torch.Tensor) else text, dtype=np.uint8).reshape(-1)
+    kind = it[:, 1]
+    if ((kind != RENDER_RECT) & (kind != RENDER_TEXT)).any():
+        raise ValueError('render_frames: item kind must be 0 (rectangle) or 1 (text)')
+    rect, txt = it[kind == RENDER_RECT], it[kind == RENDER_TEXT]
+    if len(rect) and (rect[:, 6].min() < 1 or rect[:, 6].max() > RENDER_MAX_SCALE):
+        raise ValueError(f'render_frames: rectangle thickness must lie in [1, {RENDER_MAX_SCALE}]')
+    if len(txt):
+        if txt[:, 4].min() < 1 or txt[:, 4].max() > RENDER_MAX_SCALE:
+            raise ValueError(f'render_frames: text scale must lie in [1, {RENDER_MAX_SCALE}]')
+        if txt[:, 5].min() < 0 or txt[:, 6].min() < 0 or (txt[:, 5] + txt[:, 6]).max() > tx.size:
+            raise ValueError(f'render_frames: a text range lies outside the text buffer of {tx.size} bytes')
+    return fo.astype(np.int32), np.ascontiguousarray(it.astype(np.int32)), tx
+
+
+def render_frames(ev, frame_off=None, items=None, text=None, upsample=2, out=None):
+    """Event representation [L, 2*bins, H, W] (uint8 or fp32 device tensor) -> RGB frames [L, up*H, up*W, 3] uint8 on the device: pixels
+    with events dark on white, bilinear x ``upsample`` (1 or 2), and the overlay ``items`` [n, 8] = {frame, kind, x, y, a, b, c, rgb} of
+    ``leod_render_frames_u8`` drawn in the same pass (``frame_off`` [L+1]: each frame's item range, ``text``: the bytes the text items index).
+    The overlay arrays are HOST data (lists / numpy / CPU tensors; ``text`` also bytes): checked here (ValueError), then uploaded."""
+    import numpy as np
+    if ev.dim() != 4:
+        raise ValueError(f'render_frames: ev must be [L, 2*bins, H, W], got {tuple(ev.shape)}')
+    if upsample not in (1, 2):
+        raise ValueError(f'render_frames: upsample must be 1 or 2, got {upsample}')
+    L, C2, H, W = ev.shape
+    fo, it, tx = _render_items(L, frame_off, items, text)
+    if ev.dtype not in (torch.uint8, torch.float32):
+        raise LeodHipError(f'render_frames: expected uint8 or float32 events, got {ev.dtype}')
+    _ck(ev, ev.dtype, 'ev')
+    shape = (L, upsample * H, upsample * W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=ev.device)
+    else:
+        _ck(out, torch.uint8, 'out')
+        if tuple(out.shape) != shape:
+            raise LeodHipError(f'render_frames: out must be {shape}, got {tuple(out.shape)}')
+    ws = torch.empty((L * H * W,), dtype=torch.uint8, device=ev.device)
+    d_fo = d_it = d_tx = None
+    if it is not None:                                          # the three overlay arrays in ONE host -> device copy: frame_off | items | text
+        blob = np.concatenate([fo.view(np.uint8), it.reshape(-1).view(np.uint8), tx])
+        d_blob = torch.from_numpy(blob).to(ev.device)
+        n_fo, n_it = fo.nbytes, it.nbytes
+        d_fo, d_it = d_blob[:n_fo].view(torch.int32), d_blob[n_fo:n_fo + n_it].view(torch.int32)
+        d_tx = d_blob[n_fo + n_it:] if tx.size else None
+    check(_l().leod_render_frames_u8(_p(ev), 1 if ev.dtype is torch.float32 else 0, _p(out), L, C2, H, W, int(upsample), _p(d_fo), _p(d_it),
+                                      0 if it is None else len(it), _p(d_tx), 0 if d_tx is None else d_tx.numel(), _p(ws), _stream()),
+          'render_frames')
+    return out
+
 
 # ---------------------------------------------------------------------------------------------------
 # launch plans: a captured hipGraph replayed as plain stream launches (csrc/k_plan.hip)
