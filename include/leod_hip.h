@@ -514,6 +514,37 @@ int leod_voxelize_dat_windows(const void* records, long n_events, const long* wi
                               unsigned char* out, int bins, int H, int W, int ds2, int count_cutoff, int fastmode, long* dropped,
                               leod_stream_t stream);
 
+/* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
+ * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,
+ * n_values non-zero bytes, zero padding to 16.
+ * leod_unpack_frames_u8: out [n_slots, C, H, W]; slot i decodes the blob at blob + slot_off[i] (device int64; 16-byte aligned offsets;
+ * negative, misaligned or out-of-extent = a frame of zeros); slot_flags (device int32, may be NULL) bit 0 = write the channel planes in
+ * reverse order.  Every output byte is stored exactly once by one launch (no clear, no atomics).  nbytes is the extent of the blob buffer
+ * (16-byte aligned): positions taken from blob contents are compared with it before they are read, so a malformed blob gives wrong frames
+ * and no access outside [blob, blob + nbytes) or out.  -1 for bad arguments, -3 for E >= 2^31. */
+int leod_unpack_frames_u8(const unsigned char* blob, long nbytes, const long* slot_off, const int* slot_flags, int n_slots,
+                          unsigned char* out, int C, int H, int W, leod_stream_t stream);
+/* Bytes of the largest blob a frame of E elements can take (every element non-zero), a multiple of 16; 0 for E < 1. */
+long leod_pack_frame_stride(long E);
+/* Encoder: frames [n, E] uint8 -> blob k at ws + k*stride (stride >= leod_pack_frame_stride(E), multiple of 16; ws 16-byte aligned) and its
+ * size in bytes in sizes[k] (device int64).  Three launches: per-group counts, per-frame exclusive scan, masks and values.  The bytes are
+ * those of the numpy codec. */
+int leod_pack_frames_u8(const unsigned char* frames, int n, long E, unsigned char* ws, long stride, long* sizes, leod_stream_t stream);
+/* Blob k from ws + k*stride to out + offsets[k] .. out + offsets[k+1] (device int64 [n+1], multiples of 16 within [0, out_bytes]; a frame
+ * whose offsets do not fit is skipped). */
+int leod_pack_compact_u8(const unsigned char* ws, long stride, const long* offsets, int n, unsigned char* out, long out_bytes,
+                         leod_stream_t stream);
+
+/* The same format on the HOST (csrc/packed_host.cpp; b and out are host pointers, no stream): what the frame store runs on every blob
+ * before any decoder sees it, and the dense decoder of the loaders' host path; called through ctypes, so without the GIL.
+ * leod_evp_validate: 0 = b[0 .. nbytes) is THE encoding of a frame of E elements, else the number (1 .. 12) of the first failed check of
+ * packed.validate_frame (sizes, paddings, n_masks / n_values against the popcounts, mask_base / value_base against the running sums,
+ * blocks and bits beyond E, empty masks, stored zeros).
+ * leod_evp_decode: a validated blob -> out[C * HW] (contiguous); flip != 0 writes the channel planes in reverse order; indices are
+ * still compared with their extents.  0, or -1 for bad arguments / a blob shorter than its counts say. */
+int leod_evp_validate(const unsigned char* b, long nbytes, long E);
+int leod_evp_decode(const unsigned char* b, long nbytes, int C, long HW, int flip, unsigned char* out);
+
 /* On-device spatial augmentation of uint8 event representations src/dst [T,B,C,H,W] (data/utils/augmentor.py:216-331,
  * 390-401): per batch sample b, params[b] = {hflip, mode (0 none, 1 zoom-in, 2 zoom-out), x0, y0, win_h, win_w, tflip}
  * (7 ints); flip first, then the zoom with ATen's nearest-exact index rule; zoom-out leaves zeros outside the pasted

@@ -15,6 +15,7 @@ import torch
 
 from leod_amd.data.genx_utils.labels import ObjectLabelFactory, ObjectLabels, SparselyBatchedObjectLabels
 from leod_amd.data.utils import misc
+from leod_amd.data.utils.packed import PackedSlot
 from leod_amd.data.utils.types import DatasetType, DataType
 
 _ORIGINAL_HW = {DatasetType.GEN1: (240, 304), DatasetType.GEN4: (720, 1280)}
@@ -44,11 +45,11 @@ class SequenceBase:
         self.path = str(path)
         self.seq_len = sequence_length
         self.only_load_end_labels = only_load_end_labels
-        # ---- frames: HDF5 'data' [N,20,H,W] uint8 or its raw .npy twin (leod_amd.data.utils.misc) -----------------------------
+        # ---- frames: HDF5 'data' [N,20,H,W] uint8, its raw .npy twin or its packed .evp store (leod_amd.data.utils.misc) -----------------------------
         ev_dir = get_event_representation_dir(path, ev_representation_name)
         stem = 'event_representations' + ('_ds2_nearest' if downsample_by_factor_2 else '')
-        raw, h5 = misc.resolve_link(str(ev_dir / (stem + '.npy'))), misc.resolve_link(str(ev_dir / (stem + '.h5')))
-        self.ev_repr_file = Path(raw if os.path.exists(raw) else h5)
+        h5 = str(ev_dir / (stem + '.h5'))
+        self.ev_repr_file = Path(misc.pick_frame_file(h5) or misc.resolve_link(h5))       # .npy, then .evp, then .h5
         assert self.ev_repr_file.exists(), f'{self.ev_repr_file=}'
         # only the header is read here; the store is opened on the first frame read and shared / bounded per process
         self.num_ev_repr, self.frame_shape = misc.read_frame_header(str(self.ev_repr_file))
@@ -131,7 +132,16 @@ class SequenceBase:
     # ---- sample assembly -----------------------------------------------------------------------------------------------------
     def _ev_repr_list(self, start_idx: int, end_idx: int, pad_front: int, pad_back: int, out: Optional[np.ndarray],
                       reverse: bool = False) -> List[torch.Tensor]:
-        """L = pad_front + (end - start) + pad_back frame tensors [C,H,W]: views of ``out`` [L,C,H,W] when given."""
+        """L = pad_front + (end - start) + pad_back frame tensors [C,H,W]: views of ``out`` [L,C,H,W] when given.  ``out`` may also be a
+        ``packed.PackedSlot`` (the batch assembler's device-decode path, recordings with a packed store only): it receives the frames'
+        blobs as they lie in the file, and the sample's EV_REPR stays empty until the batch is decoded."""
+        if isinstance(out, PackedSlot):
+            out.set_packed(*self.frames.read_packed(start_idx, end_idx), pad_front, reverse)
+            return []
+        return self._ev_repr_dense(start_idx, end_idx, pad_front, pad_back, out, reverse)
+
+    def _ev_repr_dense(self, start_idx: int, end_idx: int, pad_front: int, pad_back: int, out: Optional[np.ndarray],
+                       reverse: bool = False):
         n = end_idx - start_idx
         if out is None:
             buf = np.zeros((pad_front + n + pad_back,) + self.frame_shape, dtype=np.uint8)

@@ -9,7 +9,10 @@ Window rule (the project's own), D = ``duration_us``:
   * a box with timestamp t_l belongs to frame max(ceil(t_l / D) - 1, 0): a frame's labels sit at its end; boxes beyond frame N - 1 are
     dropped; where boxes of several timestamps fall in one frame, those of the latest timestamp are kept.
 
-    python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4
+``--write packed`` writes the frames as a packed store (``.evp``, data/utils/packed.py) instead of the raw ``.npy`` twin: every chunk
+of windows is encoded on the device (``ops.pack_frames``) and only the packed bytes come back.
+
+    python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed]
 """
 import argparse
 import glob
@@ -80,20 +83,25 @@ def convert_labels(boxes: np.ndarray, n_frames: int, duration_us: int, keep_clas
     return lab, starts.astype(np.int64), repr_idx.astype(np.int64)
 
 
-def voxelize_recording(records: np.ndarray, offsets: np.ndarray, frames_out: np.ndarray, bins: int, height: int, width: int, ds2: bool,
-                       device=None, frames_per_copy: int = FRAMES_PER_COPY) -> int:
+def voxelize_recording(records: np.ndarray, offsets: np.ndarray, frames_out: Optional[np.ndarray], bins: int, height: int, width: int,
+                       ds2: bool, device=None, frames_per_copy: int = FRAMES_PER_COPY, packed_writer=None) -> int:
     """Memory-mapped records [n, 2] u32 + window offsets -> ``frames_out`` [N, 2*bins, Ho, Wo] uint8 (e.g. an ``open_memmap``),
-    ``frames_per_copy`` windows at a time through one pinned record buffer and one pinned frame buffer.  -> number of dropped events."""
+    ``frames_per_copy`` windows at a time through one pinned record buffer and one pinned frame buffer.  With ``packed_writer`` (a
+    ``packed.PackedWriter``; ``frames_out`` None) every chunk is encoded on the device and only its packed bytes are copied back and
+    appended.  -> number of dropped events."""
     import torch
     from leod_amd import ops
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     n_frames = len(offsets) - 1
-    assert frames_out.shape[0] == n_frames and frames_out.dtype == np.uint8
+    assert (frames_out is None) != (packed_writer is None), 'either a dense destination or a packed writer'
     spans = [(k, min(k + frames_per_copy, n_frames)) for k in range(0, n_frames, frames_per_copy)]
     most = max([int(offsets[b] - offsets[a]) for a, b in spans] + [1])
     rec_pin = torch.empty((most, 8), dtype=torch.uint8).pin_memory()
-    out_pin = torch.empty((min(frames_per_copy, n_frames),) + tuple(frames_out.shape[1:]), dtype=torch.uint8).pin_memory()
-    rec_np, out_np = rec_pin.numpy().view('<u4'), out_pin.numpy()
+    rec_np = rec_pin.numpy().view('<u4')
+    if packed_writer is None:
+        assert frames_out.shape[0] == n_frames and frames_out.dtype == np.uint8
+        out_pin = torch.empty((min(frames_per_copy, n_frames),) + tuple(frames_out.shape[1:]), dtype=torch.uint8).pin_memory()
+        out_np = out_pin.numpy()
     dropped = torch.zeros((1,), dtype=torch.int64, device=device)
     with torch.cuda.device(device):
         for a, b in spans:
@@ -102,6 +110,10 @@ def voxelize_recording(records: np.ndarray, offsets: np.ndarray, frames_out: np.
             rec_dev = rec_pin[:hi - lo].to(device, non_blocking=True)
             out, d = ops.voxelize_dat_windows(rec_dev, offsets[a:b + 1] - lo, bins, height, width, ds2=ds2)
             dropped += d
+            if packed_writer is not None:
+                blob, blob_off = ops.pack_frames(out)           # one read-back of b - a sizes inside, then the packed bytes
+                packed_writer.append(blob.cpu().numpy(), blob_off.numpy())
+                continue
             out_pin[:b - a].copy_(out, non_blocking=True)
             torch.cuda.current_stream().synchronize()           # the pinned buffers are reused by the next span
             frames_out[a:b] = out_np[:b - a]
@@ -111,10 +123,12 @@ def voxelize_recording(records: np.ndarray, offsets: np.ndarray, frames_out: np.
 def ingest_recording(dat_fn: str, bbox_fn: str, out_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
                      keep_classes: Optional[Sequence[int]] = None, write: str = 'npy') -> Dict:
     """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
-    ``event_representations_ds2_nearest.npy`` at half resolution for Gen4), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
+    ``event_representations_ds2_nearest.npy`` at half resolution for Gen4) or, with ``write='packed'``, as the packed store of the same
+    stem (``.evp``), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
     ``keep_classes`` None: every class for Gen1, (0, 1, 2) for Gen4.  -> a small report."""
-    if write != 'npy':
-        raise ValueError(f"write={write!r}: only the raw 'npy' frame file is written (an HDF5 writer is not part of this package)")
+    if write not in ('npy', 'packed'):
+        raise ValueError(f"write={write!r}: the raw 'npy' frame file or the 'packed' store is written (an HDF5 writer is not part of "
+                         'this package)')
     dataset_type = _dataset_type(dataset_type)
     ds2 = dataset_type == DatasetType.GEN4
     hdr, records = dat_events.open_records(dat_fn)
@@ -131,15 +145,25 @@ def ingest_recording(dat_fn: str, bbox_fn: str, out_dir: str, dataset_type, dura
     ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
     os.makedirs(ev_dir, exist_ok=True)
     os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
-    frame_fn = os.path.join(ev_dir, 'event_representations' + ('_ds2_nearest' if ds2 else '') + '.npy')
+    frame_fn = os.path.join(ev_dir, 'event_representations' + ('_ds2_nearest' if ds2 else '') + ('.npy' if write == 'npy' else '.evp'))
     shape = (n_frames, 2 * bins) + ((height // 2, width // 2) if ds2 else (height, width))
-    mm = np.lib.format.open_memmap(frame_fn + '.tmp', mode='w+', dtype=np.uint8, shape=shape)
-    try:
-        dropped = voxelize_recording(records, offsets, mm, bins, height, width, ds2)
-        mm.flush()
-    finally:
-        del mm
-    os.replace(frame_fn + '.tmp', frame_fn)
+    if write == 'packed':
+        from leod_amd.data.utils.packed import PackedWriter
+        writer = PackedWriter(frame_fn, *shape[1:])              # writes frame_fn + '.tmp', renamed on close
+        try:
+            dropped = voxelize_recording(records, offsets, None, bins, height, width, ds2, packed_writer=writer)
+        except BaseException:
+            writer.abort()
+            raise
+        writer.close()
+    else:
+        mm = np.lib.format.open_memmap(frame_fn + '.tmp', mode='w+', dtype=np.uint8, shape=shape)
+        try:
+            dropped = voxelize_recording(records, offsets, mm, bins, height, width, ds2)
+            mm.flush()
+        finally:
+            del mm
+        os.replace(frame_fn + '.tmp', frame_fn)
     np.save(os.path.join(ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
     np.savez(os.path.join(out_dir, 'labels_v2', 'labels.npz'), labels=labels, objframe_idx_2_label_idx=label_idx)
     return dict(recording=out_dir, frames=n_frames, events=int(hdr.n_events), dropped_events=dropped, labelled_frames=int(len(repr_idx)),
@@ -171,13 +195,14 @@ def main(argv=None) -> int:
     ap.add_argument('--duration-us', type=int, default=50_000)
     ap.add_argument('--bins', type=int, default=10)
     ap.add_argument('--keep-classes', type=int, nargs='*', default=None)
+    ap.add_argument('--write', choices=['npy', 'packed'], default='npy', help="frame file: the raw .npy twin or the packed .evp store")
     args = ap.parse_args(argv)
     splits = [s for s in ('train', 'val', 'test') if os.path.isdir(os.path.join(args.src, s))]
     pairs = [(os.path.join(args.src, s), os.path.join(args.dst, s)) for s in splits] or [(args.src, args.dst)]
     n = 0
     for src, dst in pairs:
         n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
-                              verbose=True))
+                              write=args.write, verbose=True))
     if n == 0:
         ap.error(f'no *_td.dat under {args.src}')
     return 0

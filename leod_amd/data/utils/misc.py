@@ -5,13 +5,16 @@ data/utils/misc.py:11-99):
         event_representations_v2/stacked_histogram_dt=50_nbins=10/
             event_representations.h5 | event_representations_ds2_nearest.h5    'data' [N,20,H,W] uint8 (blosc-zstd HDF5)
             event_representations.npy | event_representations_ds2_nearest.npy   the same array as a raw .npy (memory-mapped)
+            event_representations.evp | event_representations_ds2_nearest.evp   the same array as packed sparse blobs (``packed.py``)
             objframe_idx_2_repr_idx.npy                                         int64 [n_labelled_frames]
         labels_v2/labels.npz                                                    labels (BBOX_DTYPE), objframe_idx_2_label_idx
 
 The reference reads the frames through h5py + hdf5plugin.  Neither is in the MI355X image, and a compressed HDF5 chunk
 store cannot feed >= 1.5 GB/s of uint8 voxels per GPU from Python anyway, so the frame store has two backends behind one
 interface: ``RawFrames`` (np.load(mmap_mode='r') of the .npy twin: page-cache reads straight into pinned batches) and
-``H5Frames`` (import-guarded h5py).  ``tools/h5_to_npy.py`` writes the twin once per recording."""
+``H5Frames`` (import-guarded h5py).  ``tools/h5_to_npy.py`` writes the twin once per recording.  A third backend, ``packed.PackedFrames``
+(``.evp``: sparse blobs that the device expands, a fraction of the raw twin's bytes), is preferred over the HDF5 file and comes after
+the raw twin: .npy, then .evp, then .h5."""
 import os
 from typing import Any,  List, Optional, Tuple
 
@@ -59,6 +62,36 @@ def get_ev_h5_fn(ev_dir: str, dst_name: Optional[str] = None) -> str:
 def get_ev_raw_fn(ev_dir: str, dst_name: Optional[str] = None) -> str:
     """The raw twin of the HDF5 frame file (same stem, ``.npy``)."""
     return os.path.splitext(get_ev_h5_fn(ev_dir, dst_name))[0] + '.npy'
+
+
+def get_ev_packed_fn(ev_dir: str, dst_name: Optional[str] = None) -> str:
+    """The packed twin of the HDF5 frame file (same stem, ``.evp``)."""
+    return os.path.splitext(get_ev_h5_fn(ev_dir, dst_name))[0] + '.evp'
+
+
+def frame_file_candidates(h5_fn: str) -> List[str]:
+    """The frame files of one stem in the order of preference: raw twin, packed store, HDF5."""
+    stem = os.path.splitext(h5_fn)[0]
+    return [stem + '.npy', stem + '.evp', stem + '.h5']
+
+
+def pick_frame_file(h5_fn: str) -> Optional[str]:
+    """The preferred existing frame file of a stem (links resolved), or None."""
+    for fn in frame_file_candidates(h5_fn):
+        fn = resolve_link(fn)
+        if os.path.exists(fn):
+            return fn
+    return None
+
+
+def open_frame_file(fn: str):
+    """The store behind one frame file, by its suffix."""
+    if fn.endswith('.npy'):
+        return RawFrames(fn)
+    if fn.endswith('.evp'):
+        from .packed import PackedFrames
+        return PackedFrames(fn)
+    return H5Frames(fn)
 
 
 def resolve_link(fn: str) -> str:
@@ -182,7 +215,7 @@ class FrameStoreCache:
             if st is not None:
                 self._stores.move_to_end(fn)
                 return st
-            st = RawFrames(fn) if fn.endswith('.npy') else H5Frames(fn)
+            st = open_frame_file(fn)
             self._stores[fn] = st
             while len(self._stores) > self.capacity:
                 self._stores.popitem(last=False)
@@ -207,6 +240,10 @@ def read_frame_header(fn: str):
             shape, fortran, dtype = (np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0)(f)
         assert dtype == np.uint8 and len(shape) == 4 and not fortran, (fn, dtype, shape)
         return int(shape[0]), tuple(int(x) for x in shape[1:])
+    if fn.endswith('.evp'):
+        from .packed import read_header
+        n, chw, _, _ = read_header(fn)
+        return n, chw
     st = H5Frames(fn)
     try:
         return len(st), tuple(st.shape[1:])
@@ -215,20 +252,18 @@ def read_frame_header(fn: str):
 
 
 def open_ev_repr(seq_or_ev_dir: str, dst_name: Optional[str] = None):
-    """Frame store of a recording: the raw .npy twin when it exists, else the HDF5 file."""
-    raw = resolve_link(get_ev_raw_fn(seq_or_ev_dir, dst_name))
-    if os.path.exists(raw):
-        return RawFrames(raw)
-    h5 = resolve_link(get_ev_h5_fn(seq_or_ev_dir, dst_name))
-    if os.path.exists(h5):
-        return H5Frames(h5)
-    raise FileNotFoundError(f'no event representation under {seq_or_ev_dir} (looked for {raw} and {h5})')
+    """Frame store of a recording: the raw .npy twin when it exists, else the packed .evp store, else the HDF5 file."""
+    h5 = get_ev_h5_fn(seq_or_ev_dir, dst_name)
+    fn = pick_frame_file(h5)
+    if fn is None:
+        raise FileNotFoundError(f'no event representation under {seq_or_ev_dir} (looked for {", ".join(frame_file_candidates(h5))})')
+    return open_frame_file(fn)
 
 
 def ev_repr_files(seq_or_ev_dir: str, dst_name: Optional[str] = None) -> List[str]:
-    """The frame files that exist for a recording (link targets resolved), raw twin first."""
+    """The frame files that exist for a recording (links not followed), in the order of preference: raw twin, packed store, HDF5."""
     out = []
-    for fn in (get_ev_raw_fn(seq_or_ev_dir, dst_name), get_ev_h5_fn(seq_or_ev_dir, dst_name)):
+    for fn in frame_file_candidates(get_ev_h5_fn(seq_or_ev_dir, dst_name)):
         if os.path.lexists(fn):
             out.append(fn)
     return out
@@ -238,12 +273,12 @@ def read_ev_repr(fn: str) -> np.ndarray:
     """All frames of a recording as one array [N, 20, H, W] (misc.py:83-88 of the reference reads the HDF5 file; here the raw twin is preferred)."""
     if 'event_representations_v2' not in fn:
         fn = get_ev_h5_fn(fn)
-    raw = resolve_link(os.path.splitext(fn)[0] + '.npy')
-    if os.path.exists(raw):
-        return np.load(raw)
-    store = H5Frames(resolve_link(fn))
+    picked = pick_frame_file(fn)
+    if picked is not None and picked.endswith('.npy'):
+        return np.load(picked)
+    store = open_frame_file(picked if picked is not None else resolve_link(fn))
     try:
-        return store.data[:]
+        return store.read(0, len(store)) if picked is not None and picked.endswith('.evp') else store.data[:]
     finally:
         store.close()
 

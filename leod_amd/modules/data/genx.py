@@ -106,11 +106,12 @@ class StreamLoader(_PrefetchLoader):
     """Batches of a streaming dataset (``ConcatStreamingDataPipe`` for training, ``ShardedStreamingDataPipe`` otherwise): the
     logical workers are served round-robin like DataLoader serves its worker processes; a worker that has run dry drops out."""
 
-    def __init__(self, dataset, num_workers: int, pin_memory: bool = True, prefetch: int = 3, io_threads: int = 8):
+    def __init__(self, dataset, num_workers: int, pin_memory: bool = True, prefetch: int = 3, io_threads: int = 8,
+                 packed_decode: str = 'host'):
         super().__init__(prefetch)
         self.dataset, self.num_workers = dataset, max(1, num_workers)
         first = dataset.datapipe_list[0]
-        self.assembler = BatchAssembler(first.seq_len, first.frame_shape, pin_memory, io_threads)
+        self.assembler = BatchAssembler(first.seq_len, first.frame_shape, pin_memory, io_threads, packed_decode)
         self.fill_value = getattr(dataset, 'fill_value', None)
 
     def batches(self):
@@ -128,11 +129,12 @@ class RandomLoader(_PrefetchLoader):
     """Shuffled (or class-weighted) batches of independent samples; ``drop_last`` as in the reference's training loader."""
 
     def __init__(self, dataset: CustomConcatDataset, batch_size: int, sampler=None, pin_memory: bool = True, prefetch: int = 3,
-                 io_threads: int = 8, num_workers: int = 1, rank: int = 0, world_size: int = 1, seed: int = 0, epoch: int = 0):
+                 io_threads: int = 8, num_workers: int = 1, rank: int = 0, world_size: int = 1, seed: int = 0, epoch: int = 0,
+                 packed_decode: str = 'host'):
         super().__init__(prefetch)
         self.dataset, self.batch_size, self.sampler = dataset, batch_size, sampler
         seq = dataset.datasets[0].sequence
-        self.assembler = BatchAssembler(seq.seq_len, seq.frame_shape, pin_memory, io_threads)
+        self.assembler = BatchAssembler(seq.seq_len, seq.frame_shape, pin_memory, io_threads, packed_decode)
         self.num_workers = max(1, num_workers)
         # N > 1 ranks: ONE order per epoch shared by all ranks (generator seeded seed + epoch, the same on every rank), rank r
         # takes order[r::world] -- what DistributedSampler / DistributedSamplerWrapper do for the reference under Lightning DDP
@@ -182,6 +184,10 @@ class _ConcatSlot:
     def __init__(self, dataset, local: int, drawn):
         self.dataset, self.local, (self.time_flip, self.state) = dataset, local, drawn
 
+    @property
+    def ev_repr_file(self):
+        return self.dataset.sequence.ev_repr_file
+
     def sample(self, index, out=None, time_flip=None):
         return self.dataset.read(self.local, out, self.time_flip)
 
@@ -221,7 +227,7 @@ class DataModule:
     def __init__(self, dataset_config, num_workers_train: int, num_workers_eval: int, batch_size_train: int,
                  batch_size_eval: int, pin_memory: bool = True, prefetch: int = 3, io_threads: int = 8,
                  worker_process: bool = False, device=None, ring_slots: int = 8, rank: Optional[int] = None,
-                 world_size: Optional[int] = None):
+                 world_size: Optional[int] = None, packed_decode: str = 'device'):
         assert num_workers_train >= 0 and num_workers_eval >= 0 and batch_size_train >= 1 and batch_size_eval >= 1
         self.dataset_config = dataset_config
         self.train_sampling_mode = DatasetSamplingMode(dataset_config.train.sampling)
@@ -229,7 +235,12 @@ class DataModule:
         assert self.eval_sampling_mode == DatasetSamplingMode.STREAM
         self.overall_batch_size_train, self.overall_batch_size_eval = batch_size_train, batch_size_eval
         self.overall_num_workers_train, self.overall_num_workers_eval = num_workers_train, num_workers_eval
-        self.loader_kw = dict(pin_memory=pin_memory, prefetch=prefetch, io_threads=io_threads)
+        # packed_decode: recordings read from a packed .evp store reach the device as blobs and are expanded there ('device':
+        # packed.batch_to_device, called by Module.transfer_batch_to_device) or are decoded on the reader threads ('host');
+        # trees without packed stores are not affected.  The worker-process loader always decodes on the host.
+        if packed_decode not in ('host', 'device'):
+            raise ValueError(f"packed_decode={packed_decode!r}: 'host' or 'device' expected")
+        self.loader_kw = dict(pin_memory=pin_memory, prefetch=prefetch, io_threads=io_threads, packed_decode=packed_decode)
         # worker_process: batch assembly in a forked process, frames through a HIP-registered shared ring (process_loader.py);
         # with `device` the loaders yield batches whose frames are already on that device (copied one batch ahead)
         self.worker_process, self.device, self.ring_slots = worker_process, device, ring_slots
@@ -300,7 +311,7 @@ class DataModule:
         if not self.worker_process:
             return build(**self.loader_kw)
         from leod_amd.modules.data.process_loader import ProcessLoader
-        kw = dict(self.loader_kw, pin_memory=False, prefetch=1)
+        kw = dict(self.loader_kw, pin_memory=False, prefetch=1, packed_decode='host')       # fixed-shape dense ring slots
         hw = self.get_dataloading_hw()
         L = self.dataset_config.sequence_length
         slot = L * batch_size * 20 * hw[0] * hw[1]

@@ -14,6 +14,9 @@ worker processes (modules/data/genx.py:172-232), paying a pickle + a pin-memory-
 * with ``device`` given the training process issues the slot -> HBM copy on its own stream one batch ahead (what
   ``DevicePrefetcher`` does for the in-process loaders) and returns the slot to the worker once the copy's event has completed.
 
+Recordings kept in a packed store (``.evp``, data/utils/packed.py) are decoded on the HOST by the worker here: the ring slots have the
+fixed dense shape, so ``DataModule`` builds the worker's loaders with ``packed_decode='host'``; a packed ring is not part of this loader.
+
 Without a device (CPU tests, host-side consumers) the frames of a yielded batch are views of its slot and stay valid until
 ``hold`` further batches have been drawn."""
 import collections

@@ -27,6 +27,7 @@ except ImportError:
 from leod_amd import ops
 from leod_amd.functions import WgradSide
 from leod_amd.data.genx_utils.labels import ObjectLabels, SparselyBatchedObjectLabels
+from leod_amd.data.utils.packed import PackedBatch, batch_to_device
 from leod_amd.data.utils.types import DataType, DatasetSamplingMode, ObjDetOutput
 from leod_amd.models.detection.yolox.utils.boxes import postprocess
 from leod_amd.models.detection.yolox_extension.models.detector import YoloXDetector
@@ -486,6 +487,9 @@ class Module(_Base):
                 return o.to(device, non_blocking=True)
             if isinstance(o, (ObjectLabels, SparselyBatchedObjectLabels)) or o is None or isinstance(o, (str, int, float, bool)):
                 return o
+            if isinstance(o, PackedBatch):
+                # frames still packed (loaders over .evp stores, packed_decode='device'): upload the blobs, expand them on the device
+                return batch_to_device(o, device)
             if key == DataType.EV_REPR and isinstance(o, list) and len(o) and th.is_tensor(o[0]):
                 # the L frames of a batch are views of one (pinned) [L,B,C,H,W] buffer: ONE PCIe copy, then views again
                 ev = self._stack_frames(o).to(device, non_blocking=True)

@@ -178,7 +178,7 @@ class EventSeqData:
             dirname(save_dir)/{val,test}                                                soft links to the source splits
 
         Refuses to overwrite (``os.makedirs(exist_ok=False)``).  ``num_frames`` defaults to the frame count of the source
-        recording's frame file (HDF5 or its raw .npy twin)."""
+        recording's frame file (raw .npy twin, packed .evp store or HDF5; every one that exists is linked)."""
         assert dst_name in ('gen1', 'gen4')
         assert 'train' in save_dir and dst_name in save_dir
         assert 'train' in self.path and dst_name in self.path

@@ -1588,6 +1588,54 @@ def voxelize_dat_windows(records_u8, win_off, bins, height, width, ds2=False, co
     return out, dropped
 
 
+def unpack_frames(blob_u8, slot_off, slot_flags, C, H, W, out=None):
+    """Packed event frames (``data/utils/packed.py``) -> dense uint8 [n_slots, C, H, W] in one launch.  ``blob_u8``: device uint8 buffer of
+    validated frame blobs; ``slot_off`` device int64 [n_slots]: byte offset (multiple of 16) of the blob each output frame decodes, < 0 for a
+    frame of zeros; ``slot_flags`` device int32 [n_slots] or None: bit 0 = channel planes reversed (the time-flipped view).  ``out``: any
+    contiguous device uint8 tensor of n_slots*C*H*W elements (e.g. [L, B, C, H, W]); every byte of it is written."""
+    _ck(blob_u8, torch.uint8, 'blob')
+    _ck(slot_off, torch.int64, 'slot_off')
+    _ck(slot_flags, torch.int32, 'slot_flags')
+    n_slots = slot_off.numel()
+    if slot_flags is not None and slot_flags.numel() != n_slots:
+        raise LeodHipError(f'slot_flags: {slot_flags.numel()} entries for {n_slots} slots')
+    if min(C, H, W) < 1:
+        raise LeodHipError(f'frame shape {(C, H, W)}')
+    if out is None:
+        out = torch.empty((n_slots, C, H, W), dtype=torch.uint8, device=blob_u8.device)
+    else:
+        _ck(out, torch.uint8, 'out')
+        if out.numel() != n_slots * C * H * W:
+            raise LeodHipError(f'out: {tuple(out.shape)} does not hold {n_slots} frames of {(C, H, W)}')
+    check(_l().leod_unpack_frames_u8(_p(blob_u8), blob_u8.numel(), _p(slot_off), _p(slot_flags), n_slots, _p(out), C, H, W, _stream()),
+          'unpack_frames')
+    return out
+
+
+def pack_frames(frames_u8):
+    """Dense uint8 frames [n, C, H, W] on the device -> (blob uint8 [total] on the device, offsets int64 [n + 1] on the host): frame k is
+    blob[offsets[k]:offsets[k + 1]], byte for byte what ``packed.encode_frames`` gives.  Count, scan and write passes into a workspace of
+    worst-case blobs, ONE read-back (the n sizes), then the compaction."""
+    _ck(frames_u8, torch.uint8, 'frames')
+    if frames_u8.dim() < 2:
+        raise LeodHipError(f'frames: [n, ...] expected, got {tuple(frames_u8.shape)}')
+    n = frames_u8.shape[0]
+    E = frames_u8.numel() // max(n, 1)
+    dev = frames_u8.device
+    if n == 0 or E == 0:
+        return torch.empty((0,), dtype=torch.uint8, device=dev), torch.zeros((n + 1,), dtype=torch.int64)
+    stride = int(_l().leod_pack_frame_stride(E))
+    ws = torch.empty((n * stride,), dtype=torch.uint8, device=dev)
+    sizes = torch.empty((n,), dtype=torch.int64, device=dev)
+    check(_l().leod_pack_frames_u8(_p(frames_u8), n, E, _p(ws), stride, _p(sizes), _stream()), 'pack_frames')
+    offsets = torch.zeros((n + 1,), dtype=torch.int64)
+    torch.cumsum(sizes.cpu(), 0, out=offsets[1:])
+    total = int(offsets[-1])
+    blob = torch.empty((total,), dtype=torch.uint8, device=dev)
+    check(_l().leod_pack_compact_u8(_p(ws), stride, _p(offsets.to(dev)), n, _p(blob), total, _stream()), 'pack_frames (compaction)')
+    return blob, offsets
+
+
 def mixed_density_i8(x, y, pol, t, bins, height, width, count_cutoff=None):
     """MixedDensityEventStack.construct (data/utils/representations.py:132-221): int64 events sorted in time -> int8 [bins, H, W]."""
     for a in (x, y, pol, t):

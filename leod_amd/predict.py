@@ -122,9 +122,8 @@ def read_old_and_new_data(new_dir: str, old_dir: Optional[str] = None):
     if old_dir is None:
         old_dir = os.path.join('datasets', dst_name, 'train', os.path.basename(new_dir))
     old_ev_dir = misc.get_ev_dir(old_dir)
-    raw = misc.resolve_link(misc.get_ev_raw_fn(old_ev_dir, dst_name))
-    frames = misc.RawFrames(raw) if os.path.exists(raw) else misc.H5Frames(misc.resolve_link(misc.get_ev_h5_fn(old_ev_dir, dst_name)))
-    shape = tuple(frames.data.shape)
+    frames = misc.open_ev_repr(old_ev_dir, dst_name)            # raw twin, else packed store, else HDF5
+    shape = tuple(frames.shape)
     frames.close()
     new_labels, new_idx = misc.read_npz_labels(new_dir)
     old_labels, old_idx = misc.read_npz_labels(old_dir)
