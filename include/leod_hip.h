@@ -81,6 +81,22 @@ int leod_attn_block_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw
  * The bf16 / fp16 operand format inside a family follows from the precision mode and is not part of the code.
  * leod_partition_attn_16bit_ok / _o16_ok are derivations: forward and backward with the 16-bit flags both route to F = 3. */
 int leod_partition_attn_route(int entry, int B, int H, int W, int C, int heads, int ph, int pw, int flags);
+/* The attention half of a block in one launch (16-bit precision modes, RVT stages 1-2: 80-token partitions, (C, heads) = (48, 2) | (96, 4)):
+ * y[M,C] = x + gamma * (attn(LN(x) W_qkv^T + b_qkv) W_proj^T + b_proj), i.e. leod_ln_linear_bf16_fwd -> leod_partition_attn_fwd ->
+ * leod_linear_lsres_bf16_fwd with the same rounding points (maxvit.py:185-270,343-354).  qkv16 [M,3C] / o16 [M,C] (16-bit rows of the
+ * precision mode), lse [M,heads] and stats [M,2] are each written when non-NULL -- what the three calls leave for the backward pass; all
+ * NULL is the inference case (x in, y out); qkv16, o16 and lse come all or none.  ln_w = ln_b = NULL: norm1 is the identity (the first block
+ * of a stage, maxvit_rnn.py:164-166), stats is then NULL as well.  b_qkv, b_proj and gamma may be NULL.  -3 where the kernel does not cover
+ * the geometry or mode.
+ * leod_attn_block_fwd_route: whether a BLOCK takes this call -- a query, nothing is launched, no memory is read.  flags: 1 = norm1 is a
+ * LayerNorm with weight and bias, 2 = norm1 is the identity.  40000 + 100 PT + D (40524) where the kernel covers the geometry in the current
+ * precision mode, one of the two flags is set and leod_attn_block_o16_ok holds (the block then saves the same 16-bit qkv / O as its
+ * three-launch path); 0: no partitions; -1 / -3 otherwise (mode f32, padded partitions, other (C, heads), a norm1 without weight and bias,
+ * O kept as fp32): the block runs the three calls. */
+int leod_attn_block_fwd_route(int B, int H, int W, int C, int heads, int ph, int pw, int flags);
+int leod_attn_block_fwd(const float* x, const float* ln_w, const float* ln_b, float eps, const float* Wqkv, const float* bqkv,
+                        const float* Wproj, const float* bproj, const float* gamma, float* y, void* qkv16, void* o16, float* lse,
+                        float* stats, int B, int H, int W, int C, int heads, int ph, int pw, int window, leod_stream_t stream);
 int leod_linear_lsres_bf16_fwd(const void* a16, const float* W, const float* bias, const float* gamma, const float* res, float* out,
                                int M, int N, int K, leod_stream_t stream);
 /* out16[M,N] = bf16(LN(x) W^T + bias), stats_out [M,2]; -3 unless the row-streaming kernel covers (M, N, K) in precision mode bf16. */

@@ -42,3 +42,28 @@ static int attn_route(int entry, int B, int H, int W, int C, int heads, int ph, 
     if (!(DCH == 2 ? pt8 : DCH == 1 && (PT == 1 || PT == 2 || PT == 4 || PT == 5))) return LEOD_ERR_UNSUPPORTED;
     return empty ? 0 : AR_REG + 100 * PT + 16 * DCH;
 }
+
+// ---- the one-launch attention sub-block (k_attn_block.hip): y = x + gamma * proj(attn(qkv(LN(x)))) -------------------------------------
+// the flags of leod_attn_block_fwd_route: what the block knows about its parameters
+enum : int { ABF_LN_AFFINE = 1, ABF_NO_NORM = 2 };            // norm1 is a LayerNorm with weight and bias | norm1 is the identity (first block of a stage)
+//   F = 4   attn_block_fwd_kernel<C, heads>: 80-token partitions, d = 24; code 40000 + 100 PT + D like the families above
+enum : int { AR_BLOCK = 40000 };
+extern "C" int leod_attn_block_o16_ok(int B, int H, int W, int C, int heads, int ph, int pw);
+
+// What the kernel itself covers: a 16-bit precision mode and full 80-token partitions of an instantiated (C, heads).  leod_attn_block_fwd
+// launches on this value.
+static int attn_block_kernel_route(int B, int H, int W, int C, int heads, int ph, int pw) {
+    if (heads <= 0 || ph <= 0 || pw <= 0 || B < 0 || H <= 0 || W <= 0 || C != heads * (C / heads) || H % ph || W % pw) return LEOD_ERR_ARG;
+    if (leod_precision() != 1 || ph * pw != 80 || (long)B * H * W > 0x7fffffffL) return LEOD_ERR_UNSUPPORTED;
+    if (!((C == 48 && heads == 2) || (C == 96 && heads == 4))) return LEOD_ERR_UNSUPPORTED;      // RVT-S stages 1 and 2
+    return B == 0 ? 0 : AR_BLOCK + 100 * 5 + 24;
+}
+// The routing function of the block's forward: launches nothing, reads no device memory.  Positive only where the kernel covers the
+// geometry AND the block keeps O / dO as 16-bit rows (leod_attn_block_o16_ok: the saved tensors are those of the three-launch path, so
+// the backward pass is the same either way) AND norm1 is a LayerNorm with weight and bias, or the identity; everything else is LEOD_ERR_UNSUPPORTED: the block runs its three launches.
+static int attn_block_fwd_route(int B, int H, int W, int C, int heads, int ph, int pw, int flags) {
+    const int k = attn_block_kernel_route(B, H, W, C, heads, ph, pw);
+    if (k < 0) return k;
+    if (!(flags & (ABF_LN_AFFINE | ABF_NO_NORM)) || !leod_attn_block_o16_ok(B ? B : 1, H, W, C, heads, ph, pw)) return LEOD_ERR_UNSUPPORTED;
+    return k;
+}

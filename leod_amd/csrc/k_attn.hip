@@ -12,13 +12,8 @@
 // already laid out as the A operand of the P.V MFMA (k index = lane>>4): no LDS, no shuffles apart
 // from the 2-step cross-row-group reductions.  P = 80 tokens -> 5 key tiles, 20 accumulator VGPRs.
 #include "attn_route.hpp"
+#include "attn_common.hpp"                       // AttnGeom, token_row, the 16-bit tile fragments (shared with k_attn_block.hip)
 #include <type_traits>
-
-struct AttnGeom {
-    int B, H, W, C, heads, d, ph, pw, window;   // window: 1 = window partition, 0 = grid partition
-    int fmt;                                    // precision mode bf16, LDS kernels only: bit 0 = qkv holds bf16, bit 1 = dqkv is written as
-                                                // bf16 (q, k, v only ever enter bf16 MFMAs; dqkv's consumers feed bf16 MFMAs)
-};
 
 // Row (token) addressing without integer division in the inner loops: every lane computes, ONCE per wave, the row of
 // the tokens 16*mt + (lane & 15) of its partition (PT values in registers); the row of any other token of the
@@ -322,15 +317,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
 // Outputs go back through LDS so that a wave instruction stores whole per-token segments (O: d floats per head,
 // dqkv: the full 3d*HG segment with dq, dk, dv of both passes of the fused backward).
 // =====================================================================================================================
-__device__ __forceinline__ long token_row(const AttnGeom& g, int p, int t) {
-    const int nH = g.H / g.ph, nW = g.W / g.pw, per = nH * nW;
-    if (t >= g.ph * g.pw) return -1;
-    const int b = p / per, rem = p - b * per;
-    const int py = rem / nW, px = rem - py * nW;
-    const int ty = t / g.pw, tx = t - ty * g.pw;
-    return g.window ? ((long)b * g.H + (long)py * g.ph + ty) * g.W + (long)px * g.pw + tx
-                    : ((long)b * g.H + py + (long)ty * nH) * g.W + px + (long)tx * nW;
-}
 __device__ __forceinline__ f4 lds4(const float* p, bool ok) { return ok ? *reinterpret_cast<const f4*>(p) : zero4(); }
 
 // Fragment of one token row along the head dimension for the contractions over d (Q K^T, dO V^T): full 16-wide chunks in the
@@ -727,27 +713,7 @@ __global__ __launch_bounds__(64 * PT * HG) void attn_bwd_lds_kernel(const float*
 //     zeroed on ONE operand of every product (the wave's own q / dO / k / v fragment, loaded once), the streamed operand stays raw;
 //   * 32 KB of LDS per (partition, two heads) instead of 64: three 10-wave workgroups per CU.
 // =====================================================================================================================
-template <int D, int HG>
-struct A16L {
-    static constexpr int RW = HG * 3 * D, RWD = HG * D;                     // bf16 elements of a staged qkv / dO row
-    static constexpr int SD = (RW / 2 + 7) / 16 * 16 + 8;                   // row strides in dwords, == 8 (mod 16)
-    static constexpr int SDD = (RWD / 2 + 7) / 16 * 16 + 8;
-    static_assert(RW % 8 == 0 && RWD % 8 == 0 && SD >= RW / 2 && SDD >= RWD / 2, "rows are staged in units of 8 elements");
-};
-typedef unsigned u4v_ __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s4 lds_s4_;
-// head-dimension fragment: 8 bf16 of row `row` starting at dword `dw` (+ 4 rg)
-__device__ __forceinline__ s8v a16_frag(const unsigned* base, int row, int sd, int dw, int rg) {
-    return __builtin_bit_cast(s8v, *reinterpret_cast<const u4v_*>(base + row * sd + dw + 4 * rg));
-}
-template <int D> __device__ __forceinline__ s8v a16_mask(s8v v, int rg) {   // d = 24: k = 24 .. 31 belongs to the next part of the row
-    if (D == 24 && rg == 3) v = s8v{0, 0, 0, 0, 0, 0, 0, 0};
-    return v;
-}
-// token-dimension fragment: element [4 rg + j][16-column tile at dword dw] of the 16-row tile starting at row0, for j = 0 .. 3
-__device__ __forceinline__ s4 a16_tfrag(const unsigned* base, int row0, int sd, int dw, int i, int rg) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_*)(base + (row0 + 4 * rg + (i >> 2)) * sd + dw + 2 * (i & 3)));
-}
+// (A16L, a16_frag, a16_mask, a16_tfrag: attn_common.hpp)
 
 // stage rows of 8-element units: src rows are bf16 (SRC16) or fp32; all global loads first, then the LDS stores.  The padding units of a
 // row (SDW / 4 > UNITS) and the 8 slack dwords behind the last row are ZEROED: the fragments of the last part of a row read 8 elements

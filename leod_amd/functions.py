@@ -325,14 +325,22 @@ class AttnBlockFn(Function):
         need = any(ctx.needs_input_grad)
         (n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, g1, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, g2) = params
         heads, part, window = mod.self_attn.num_heads, mod.partition_size, mod.partition_window
-        # precision mode bf16: where the LDS attention kernels cover the geometry, qkv (and dqkv in backward) live in HBM as bf16
-        q16 = ops.partition_attn_16bit_ok(x.shape[0], x.shape[1], x.shape[2], x.shape[3], heads, part)
-        qkv, _, st1 = ops.ln_linear_fwd(x, n1w, n1b, qkv_w, qkv_b, want_stats=need or q16, out_bf16=q16)
-        # ... and the attention output O (dO in backward) as bf16 rows where every consumer has the 16-bit path
-        o16 = q16 and ops.attn_block_o16_ok(x.shape[0], x.shape[1], x.shape[2], x.shape[3], heads, part)
-        o, lse = ops.partition_attn_fwd(qkv, heads, part, window, want_lse=need, out_bf16=o16)
-        # the pre-LayerScale outputs are NOT stored: dgamma is recovered from the un-scaled weight gradient in backward
-        y, _ = ops.linear_lsres_fwd(o, proj_w, proj_b, g1, x, want_t=False, a_gelu=False)
+        geom = (x.shape[0], x.shape[1], x.shape[2], x.shape[3], heads, part)
+        # norm1: a LayerNorm with weight and bias, or the identity (the first block of a stage)
+        n1 = ops.ABF_LN_AFFINE if n1w is not None and n1b is not None else (ops.ABF_NO_NORM if n1w is None and n1b is None else 0)
+        if ops.ATTN_BLOCK_FUSED and x.dim() == 4 and ops.attn_block_fwd_route(*geom, flags=n1) > 0:
+            # 16-bit modes, stages 1-2: the whole attention half in one launch (csrc/k_attn_block.hip); it leaves the tensors of the
+            # three launches below behind when a backward pass is to come, and none of them otherwise
+            y, qkv, st1, o, lse = ops.attn_block_fwd(x, n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, g1, heads, part, window, want_saved=need)
+        else:
+            # precision mode bf16: where the LDS attention kernels cover the geometry, qkv (and dqkv in backward) live in HBM as bf16
+            q16 = ops.partition_attn_16bit_ok(*geom)
+            qkv, _, st1 = ops.ln_linear_fwd(x, n1w, n1b, qkv_w, qkv_b, want_stats=need or q16, out_bf16=q16)
+            # ... and the attention output O (dO in backward) as bf16 rows where every consumer has the 16-bit path
+            o16 = q16 and ops.attn_block_o16_ok(*geom)
+            o, lse = ops.partition_attn_fwd(qkv, heads, part, window, want_lse=need, out_bf16=o16)
+            # the pre-LayerScale outputs are NOT stored: dgamma is recovered from the un-scaled weight gradient in backward
+            y, _ = ops.linear_lsres_fwd(o, proj_w, proj_b, g1, x, want_t=False, a_gelu=False)
         # precision mode bf16, stage 1: the whole MLP in one launch, the hidden in registers (csrc/k_mlp.hip); with a backward pass to
         # come it also leaves the fp16 pre-activation and the LayerNorm statistics behind
         fused = ops.mlp_fwd_fused(y, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, g2, want_saved=need)

@@ -298,6 +298,48 @@ def partition_attn_route(entry, B, H, W, C, heads, part, flags=0) -> int:
     return int(_l().leod_partition_attn_route(entry, B, H, W, C, heads, part[0], part[1], flags))
 
 
+ATTN_BLOCK_FUSED = True     # the attention half of a block in one launch where attn_block_fwd_route says so; False: always the three launches
+ABF_LN_AFFINE, ABF_NO_NORM = 1, 2   # flags of ``attn_block_fwd_route`` (include/leod_hip.h): norm1 is a LayerNorm with weight and bias | the identity
+_ATTN_BLOCK_ROUTES = {}
+
+
+def attn_block_fwd_route(B, H, W, C, heads, part, flags=ABF_LN_AFFINE) -> int:
+    """Whether an attention block of this geometry runs ``attn_block_fwd`` in the current precision mode: a positive route code, or the
+    negative error code that sends it to its three launches (``leod_attn_block_fwd_route`` in include/leod_hip.h; nothing is launched).
+    Remembered per precision mode: the step path asks on every block."""
+    key = (int(_l().leod_get_precision()), BF16_GRADS, B, H, W, C, heads, part[0], part[1], flags)
+    code = _ATTN_BLOCK_ROUTES.get(key)
+    if code is None:
+        if len(_ATTN_BLOCK_ROUTES) > 4096:
+            _ATTN_BLOCK_ROUTES.clear()
+        code = int(_l().leod_attn_block_fwd_route(B, H, W, C, heads, part[0], part[1], flags)) if BF16_GRADS else -3
+        _ATTN_BLOCK_ROUTES[key] = code
+    return code
+
+
+def attn_block_fwd(x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, gamma, heads, part, window, want_saved=False, eps=1e-5):
+    """y = x + gamma * proj(attention(qkv(LN(x)))) on the partitions of the map x [B,H,W,C] in ONE launch (csrc/k_attn_block.hip)
+    -> (y, qkv, stats, o, lse); the last four are what ln_linear_fwd / partition_attn_fwd leave for the backward pass (16-bit qkv and O
+    rows of the precision mode; stats is None when ln_w and ln_b are None: norm1 is the identity) when want_saved, else None.  Raises where the kernel does not cover the geometry: ask
+    ``attn_block_fwd_route`` first."""
+    for t, n in ((x, 'x'), (ln_w, 'ln_w'), (ln_b, 'ln_b'), (qkv_w, 'qkv_w'), (qkv_b, 'qkv_b'), (proj_w, 'proj_w'), (proj_b, 'proj_b'),
+                 (gamma, 'gamma')):
+        _ck(t, name=n)
+    B, H, W, C = x.shape
+    M = B * H * W
+    y = _empty(x.shape, x)
+    qkv = o = lse = stats = None
+    if want_saved:
+        qkv = torch.empty((B, H, W, 3 * C), dtype=act16_dtype(), device=x.device)
+        o = torch.empty((B, H, W, C), dtype=act16_dtype(), device=x.device)
+        lse = _empty((B, H, W, heads), x)
+        stats = _empty((M, 2), x) if ln_w is not None else None
+    check(_l().leod_attn_block_fwd(_p(x), _p(ln_w), _p(ln_b), eps, _p(qkv_w), _p(qkv_b), _p(proj_w), _p(proj_b), _p(gamma), _p(y),
+                                   _p(qkv), _p(o), _p(lse), _p(stats), B, H, W, C, heads, part[0], part[1], 1 if window else 0, _stream()),
+          'attn_block_fwd')
+    return y, qkv, stats, o, lse
+
+
 def partition_attn_bwd(qkv, dout, lse, heads, part, window):
     q16 = _is16(qkv)
     _ck(qkv, act16_dtype() if q16 else F32, 'qkv')
@@ -1946,7 +1988,7 @@ class _ProbedLib:
         fn = self._cache.get(name)
         if fn is None:
             real = getattr(self._lib, name)
-            if not name.startswith('leod_') or name.endswith(('_ok', '_mode', '_bytes', '_floats', 'get_precision', 'set_precision')):
+            if not name.startswith('leod_') or name.endswith(('_ok', '_mode', '_bytes', '_floats', '_route', 'get_precision', 'set_precision')):
                 fn = real
             else:
                 probe = self._probe
