@@ -235,7 +235,8 @@ int leod_linear_wgrad_route(int M, int N, int K, long lddy, long ldx, long ldx2,
  *   3000 + NTW            persistent wide-tile kernel, workgroups of 64 NTW columns (NTW 3, 4)
  *   4000 + 100 NT + KCH   LDS-staged kernel, NT blocks of 16 columns, K chunks of KCH (48, 64), two-phase row loader
  *   5000 + 100 NT + KCH   the same with the plain row loader
- *   6000 + 10 NT + KS     register-direct kernel, K split over KS waves (1, 4) */
+ *   6000 + 10 NT + KS     register-direct kernel, K split over KS waves (1, 4)
+ *   0                     M <= 0 with valid arguments: nothing to do, the call returns 0 */
 int leod_linear_route(int entry, int M, int N, int K, long lda, long ldo, int a16, int out16, int flags, int nsplit);
 
 /* LayerNorm over channels (eps 1e-5), maxvit.py:172-178 and its autograd. */

@@ -555,13 +555,16 @@ struct EpStore {
                 if (act == ACT_AFFINE_SILU) v = siluf_(v * sc + sh);
                 if (act == ACT_MUL_GELU_GRAD && ok) v *= gelu_erf_grad(aux[row * ldaux + n]);
                 if (ok) {
+                    // v becomes the STORED value: the column sums below are those of what the buffer holds, as in run_rows
                     if (nsplit > 0 && n >= nsplit) {
                         float* p = out2 + row * ld2 + (n - nsplit);
-                        *p = accumulate ? *p + v : v;
+                        if (accumulate) v += *p;
+                        *p = v;
                     } else {
                         float* p = out + row * ld + n;
                         if (addsrc) v += addsrc[row * ld + n];
-                        *p = accumulate ? *p + v : v;
+                        if (accumulate) v += *p;
+                        *p = v;
                         if (act == ACT_GELU_DUAL) out2[row * ld2 + n] = gelu_erf(v);
                     }
                     s1 += v; s2 += v * v;

@@ -531,6 +531,7 @@ static LinearProb linear_prob(int entry, int M, int N, int K, long lda, long ldo
 //   4000 + 100 NT + KCH    gemm_lds_kernel<NT, KCH> with the two-phase loader ALRowsM (KCH 48 | 64)
 //   5000 + 100 NT + KCH    gemm_lds_kernel<NT, KCH> with the plain loader ALRows
 //   6000 + 10 NT + KS      gemm16_kernel<NT, KS> (KS = 4: K split over the waves, else 1)
+//   0                      M <= 0: nothing to do, the entry returns LEOD_OK
 //   < 0                    LEOD_ERR_*: what the entry returns
 enum : int { LR_RS48 = 1000, LR_NARROW = 2000, LR_WIDE = RG_WIDE, LR_LDS2P = RG_TWO_PHASE, LR_LDS = RG_PLAIN, LR_GEMM16 = 6000 };
 static int linear_route(const LinearProb& p) {
@@ -540,6 +541,7 @@ static int linear_route(const LinearProb& p) {
     if ((kc & e.kc_mask) || (p.lda & e.lda_mask)) return LEOD_ERR_ARG;
     if (e.needs16 && !bf) return e.needs16;
     if (p.entry == LE_DGRAD_LNBWD) {                // the narrow kernel with the LayerNorm backward in its epilogue, or nothing
+        if (M <= 0) return 0;
         if (a_bf16 && use_rowstream_narrow96(M, kc, nout)) return LR_NARROW + kc / 16;
         if (!use_rowstream_narrow(M, kc, nout)) return LEOD_ERR_UNSUPPORTED;
         return (a_bf16 && !bf) ? LEOD_ERR_ARG : LR_NARROW + kc / 16;         // bf16 dy in mode f32: refused only after the narrow test
@@ -551,6 +553,7 @@ static int linear_route(const LinearProb& p) {
         if (out16 && (!bf || extras || p.act || (nout & 3) || !lds)) return LEOD_ERR_UNSUPPORTED;
         if (p.dres && (p.nsplit > 0 || p.accumulate)) return LEOD_ERR_ARG;
     }
+    if (M <= 0) return 0;                           // no rows: every entry returns LEOD_OK, also those that have no kernel for small M
     if (!a_bf16 && p.a_dense && p.out_dense && !extras && (!p.ln || p.stats) && !(p.entry == LE_DGRAD && out16)) {
         if (e.narrow && !p.tout && !p.kscale && !p.act) {
             if (e.narrow96 && kc == 384 && use_rowstream_narrow96(M, kc, nout)) return LR_NARROW + 24;
@@ -629,7 +632,7 @@ static int launch_rowstream_narrow(const LinearProb& p, const LinearArgs& a, hip
 }
 template <int E>
 static int launch_linear(int route, const LinearProb& p, const LinearArgs& a, hipStream_t s) {
-    if (route < 0) return route;
+    if (route <= 0) return route;
     static constexpr LinearEntryInfo e = kLinearEntry[E];
     const int par = route % 1000;
     if (route < LR_NARROW) {

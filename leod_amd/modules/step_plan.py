@@ -50,16 +50,31 @@ class PlanRecorder:
         self.max_lanes, self.pool = max_lanes, pool
         self.segments: List[Tuple[Optional[ops.LaunchPlan], Any]] = []
         self.graph = None
+        self.capturing = False
 
     def begin(self):
         self.graph = th.cuda.CUDAGraph(keep_graph=True)
         if self.pool is None:
             self.pool = th.cuda.graph_pool_handle()          # one private pool for every segment of the step (forward and backward)
-        self.graph.capture_begin(pool=self.pool, capture_error_mode='relaxed')
+        ops.LaunchPlan.capture_opened()                      # from here to capture_end no launch plan is destroyed (ops.LaunchPlan.close parks it)
+        try:
+            self.graph.capture_begin(pool=self.pool, capture_error_mode='relaxed')
+        except BaseException:
+            ops.LaunchPlan.capture_closed()
+            raise
+        self.capturing = True
+
+    def _capture_end(self):
+        try:
+            self.graph.capture_end()
+        finally:
+            if self.capturing:
+                self.capturing = False
+                ops.LaunchPlan.capture_closed()
 
     def end(self, callback=None):
         Fn.WgradSide.join()                                  # every forked stream back on the capturing stream before the capture ends
-        self.graph.capture_end()
+        self._capture_end()
         try:
             plan = ops.LaunchPlan(self.graph, self.max_lanes)
         except LeodHipError as e:
@@ -294,7 +309,7 @@ def _abort_captures(capture_stream, *recs):
             if rec is not None and rec.graph is not None:
                 try:
                     Fn.WgradSide.join()
-                    rec.graph.capture_end()
+                    rec._capture_end()
                 except Exception:                             # noqa: BLE001
                     pass
             if rec is not None:

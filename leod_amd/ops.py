@@ -1835,11 +1835,49 @@ class LaunchPlan:
     def dump(self, path: str):
         check(_l().leod_plan_dump(self.handle, path.encode()), 'plan_dump')
 
+    # A plan must not be torn down while a stream capture is open: leod_plan_destroy destroys streams and events, and dropping the CUDAGraph
+    # destroys a hipGraph and releases its memory pool -- inside a capture the graph's destructor aborts the process.  close() is also the
+    # finaliser, and the cyclic garbage collector runs whenever it likes: in the middle of the capture of a LATER step it finalises the plans
+    # of a module that an earlier step dropped.  Such plans are parked here and released when the last open capture has ended.
+    _captures_open = 0
+    _parked: list = []
+
+    @staticmethod
+    def _stream_capturing() -> bool:
+        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+    @classmethod
+    def capture_opened(cls):
+        cls._captures_open += 1
+
+    @classmethod
+    def capture_closed(cls):
+        cls._captures_open = max(0, cls._captures_open - 1)
+        cls.release_parked()
+
+    @classmethod
+    def release_parked(cls):
+        if cls._captures_open or not cls._parked or cls._stream_capturing():
+            return
+        parked, cls._parked = cls._parked, []
+        for handle, graph in parked:
+            if handle:
+                _l().leod_plan_destroy(handle)
+            del graph
+
     def close(self):
-        if getattr(self, 'handle', 0):
-            _l().leod_plan_destroy(self.handle)
-            self.handle = 0
-        self.graph = None
+        cls = type(self)
+        handle, graph = getattr(self, 'handle', 0), getattr(self, 'graph', None)
+        self.handle, self.graph = 0, None
+        if not handle and graph is None:
+            return
+        if cls._captures_open or cls._stream_capturing():
+            cls._parked.append((handle, graph))
+            return
+        if handle:
+            _l().leod_plan_destroy(handle)
+        del graph
+        cls.release_parked()
 
     def __del__(self):
         try:
