@@ -530,6 +530,28 @@ int leod_mixed_density_i8(const long* x, const long* y, const long* pol, const l
 int leod_voxelize_dat_windows(const void* records, long n_events, const long* win_off, int n_win, int* counts_ws, int ws_windows,
                               unsigned char* out, int bins, int H, int W, int ds2, int count_cutoff, int fastmode, long* dropped,
                               leod_stream_t stream);
+/* Metavision RAW payloads (csrc/k_evt.hip; layouts and the project's rules: DESIGN.md section 1) -> the 8-byte .dat records above, in
+ * stream order, one chunk of words per scan + emit pair.  fmt 2: EVT2, little-endian u32 words, type in bits 31:28 (0 / 1 CD_OFF / CD_ON:
+ * low 6 time bits in 27:22, x in 21:11, y in 10:0; 8 EVT_TIME_HIGH: bits 27:0; A, E, F ignored; others unknown), t = (high << 6) | low.
+ * fmt 3: EVT3, little-endian u16 words, type in bits 15:12 (0 ADDR_Y: y = bits 10:0; 2 ADDR_X: one event, x = bits 10:0, p = bit 11;
+ * 3 VECT_BASE_X: base = bits 10:0, p = bit 11; 4 VECT_12 / 5 VECT_8: an event at base + i for every set bit i of bits 11:0 / 7:0 in
+ * ascending i, then base += 12 / 8; 6 TIME_LOW, 8 TIME_HIGH: bits 11:0; 7, A, E, F ignored; others unknown),
+ * t = ((wraps * 4096 + high) << 12) | low, one wrap where TIME_HIGH falls by 2048 or more.  Times are shifted by the file's first
+ * TIME_HIGH (<< 12 / << 6); an event before every field it needs is set is dropped and counted; x and y are not range-checked.
+ * state: 16 longs on the device, carried from chunk to chunk (all zero before the first chunk; state_out may be state_in):
+ *   [0] valid bits (1 time high, 2 time low, 4 row, 8 vector base) [1] last TIME_HIGH [2] clock wraps [3] TIME_LOW [4] row [5] vector base
+ *   [6] vector polarity [7] time base [8] events [9] early events [10] ignored words [11] unknown words [12] overflow: a shifted time
+ *   outside [0, 2^32) was met (its record holds the low 32 bits) [13] fmt of the last chunk [14] events of the last chunk [15] 0.
+ * leod_evt_query (host only): *tile_words = words per tile, *tiles_per_pass = tile summaries the scan workgroup takes per pass,
+ *   *ws_bytes = workspace for a chunk of n_words words (any may be NULL).
+ * leod_evt_scan: per-tile reduce + the one-workgroup scan (2 launches): fills ws and writes state_out, so state_out[14] sizes the output.
+ * leod_evt_emit: same words, same ws; stores the records (out: 8-byte aligned, capacity in records; nothing is stored at or beyond
+ *   capacity) and ORs the overflow flag into state_out[12].  words: 16-byte aligned; ws: 8-byte aligned.  -1 for bad arguments. */
+int leod_evt_query(long n_words, int* tile_words, int* tiles_per_pass, long* ws_bytes);
+int leod_evt_scan(const void* words, long n_words, int fmt, const long* state_in, long* state_out, void* ws, long ws_bytes,
+                  leod_stream_t stream);
+int leod_evt_emit(const void* words, long n_words, int fmt, const void* ws, long ws_bytes, void* out, long capacity, long* state_out,
+                  leod_stream_t stream);
 
 /* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
  * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,

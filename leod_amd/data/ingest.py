@@ -1,5 +1,6 @@
-"""Recording ingestion: a raw Prophesee recording (``*_td.dat`` events + ``*_bbox.npy`` boxes) to the dataset tree the loaders read
-(layout: ``leod_amd/data/utils/misc.py``).  The reference has no such stage (its docs/install.md points at pre-voxelised downloads).
+"""Recording ingestion: a raw Prophesee recording (``*_td.dat`` or Metavision ``*.raw`` events + ``*_bbox.npy`` boxes) to the dataset tree
+the loaders read (layout: ``leod_amd/data/utils/misc.py``).  The reference has no such stage (its docs/install.md points at pre-voxelised
+downloads).
 
 The record bytes go to the device as they lie in the file; ``ops.voxelize_dat_windows`` (csrc/k_ingest.hip) decodes them and writes
 the stacked histogram of every window.  The host only reads timestamps (sortedness, window offsets), moves bytes and writes labels.
@@ -12,7 +13,11 @@ Window rule (the project's own), D = ``duration_us``:
 ``--write packed`` writes the frames as a packed store (``.evp``, data/utils/packed.py) instead of the raw ``.npy`` twin: every chunk
 of windows is encoded on the device (``ops.pack_frames``) and only the packed bytes come back.
 
-    python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed]
+A ``.raw`` file (EVT2 / EVT3; ``data/utils/raw_events.py``) goes to the device as payload bytes, a chunk at a time; ``ops.decode_evt``
+(csrc/k_evt.hip) turns each chunk into the same 8-byte records, which then take the path above window by window.  ``--unlabelled ok``
+accepts recordings without a box file (trees with zero labels, to be pseudo-labelled).
+
+    python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed] [--unlabelled error|ok]
 """
 import argparse
 import glob
@@ -33,6 +38,7 @@ _FIELD_ALIASES = {'ts': 't', 'confidence': 'class_confidence'}
 SENSOR_HW = {DatasetType.GEN1: (240, 304), DatasetType.GEN4: (720, 1280)}
 DEFAULT_KEEP_CLASSES = {DatasetType.GEN1: None, DatasetType.GEN4: (0, 1, 2)}        # the three classes the Gen4 configs train on
 FRAMES_PER_COPY = 32             # windows per device call and per copy through the pinned buffer
+RAW_CHUNK_BYTES = 64 << 20       # payload bytes of a .raw file per decode call (a multiple of 4: whole EVT2 and EVT3 words)
 
 
 def _dataset_type(dataset_type) -> DatasetType:
@@ -120,16 +126,176 @@ def voxelize_recording(records: np.ndarray, offsets: np.ndarray, frames_out: Opt
     return int(dropped.item())
 
 
-def ingest_recording(dat_fn: str, bbox_fn: str, out_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
-                     keep_classes: Optional[Sequence[int]] = None, write: str = 'npy') -> Dict:
+def _npy_header(shape) -> bytes:
+    """The header ``np.lib.format.open_memmap`` writes for a uint8 array of this shape (format 1.0)."""
+    import io
+    buf = io.BytesIO()
+    np.lib.format.write_array_header_1_0(buf, dict(descr=np.lib.format.dtype_to_descr(np.dtype(np.uint8)), fortran_order=False,
+                                                   shape=tuple(int(v) for v in shape)))
+    return buf.getvalue()
+
+
+class _NpyStream:
+    """A dense frame file whose number of frames is known only at the end, byte for byte the file ``open_memmap`` would have made: the
+    frames are appended to ``fn + '.tmp'`` behind room for the header (``reserve`` bytes; None: the header of an empty file -- NumPy pads
+    it to 64 bytes with room for the first axis to grow, so its length rarely depends on N); ``close`` writes the header of the final
+    shape in front and renames the file.  Where that header does not have the reserved length the frames are moved once, through
+    ``fn + '.body'``."""
+
+    def __init__(self, fn: str, frame_shape, reserve: Optional[int] = None):
+        self.fn, self.frame_shape, self.n = fn, tuple(int(s) for s in frame_shape), 0
+        self.reserve = len(_npy_header((0,) + self.frame_shape)) if reserve is None else int(reserve)
+        self._f = open(fn + '.tmp', 'wb')
+        self._f.write(b'\0' * self.reserve)
+
+    def append(self, frames: np.ndarray) -> None:
+        assert frames.dtype == np.uint8 and tuple(frames.shape[1:]) == self.frame_shape
+        self._f.write(memoryview(np.ascontiguousarray(frames)).cast('B'))
+        self.n += len(frames)
+
+    def close(self) -> None:
+        header = _npy_header((self.n,) + self.frame_shape)
+        if len(header) == self.reserve:
+            self._f.seek(0)
+            self._f.write(header)
+            self._f.close()
+        else:
+            import shutil
+            self._f.close()
+            os.replace(self.fn + '.tmp', self.fn + '.body')
+            with open(self.fn + '.body', 'rb') as src, open(self.fn + '.tmp', 'wb') as dst:
+                dst.write(header)
+                src.seek(self.reserve)
+                shutil.copyfileobj(src, dst, 1 << 24)
+            os.remove(self.fn + '.body')
+        os.replace(self.fn + '.tmp', self.fn)
+
+    def abort(self) -> None:
+        self._f.close()
+        for fn in (self.fn + '.body', self.fn + '.tmp'):
+            if os.path.exists(fn):
+                os.remove(fn)
+
+
+def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: bool, duration_us: int, bins: int, height: int, width: int,
+                           ds2: bool, what: str, device=None, raw_chunk_bytes: int = RAW_CHUNK_BYTES,
+                           frames_per_copy: int = FRAMES_PER_COPY) -> Dict:
+    """Memory-mapped payload bytes of a .raw file -> frames appended to ``sink`` (``_NpyStream`` or, with ``packed``, a ``PackedWriter``).
+    ``raw_chunk_bytes`` of payload at a time go through one pinned buffer and are decoded with the carried state (``ops.decode_evt``);
+    sortedness and the window offsets of the decoded times are found on the device; every window that is complete -- a later event has
+    been seen -- is voxelised by ``ops.voxelize_dat_windows``, the records of the last, incomplete one are carried into the next chunk.
+    -> dict(frames, dropped_events and the decoder's counters)."""
+    import torch
+    from leod_amd import ops
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    raw_chunk_bytes = int(raw_chunk_bytes)
+    if raw_chunk_bytes < 4 or raw_chunk_bytes % 4:
+        raise ValueError(f'raw_chunk_bytes={raw_chunk_bytes}: a positive multiple of 4 expected')
+    D = int(duration_us)
+    pin = torch.empty((min(raw_chunk_bytes, max(len(payload), 4)),), dtype=torch.uint8).pin_memory()
+    pin_np = pin.numpy()
+    dropped = torch.zeros((1,), dtype=torch.int64, device=device)
+    state, carry, done, t_last = None, torch.empty((0, 8), dtype=torch.uint8, device=device), 0, 0
+
+    def emit(rec, off):                                          # windows `done` .. of rec, offsets [k + 1] on the device
+        nonlocal done, dropped
+        n_win = off.numel() - 1
+        for a in range(0, n_win, frames_per_copy):
+            b = min(a + frames_per_copy, n_win)
+            lo, hi = int(off[a]), int(off[b])
+            out, d = ops.voxelize_dat_windows(rec[lo:hi].reshape(-1), off[a:b + 1] - lo, bins, height, width, ds2=ds2)
+            dropped += d
+            if packed:
+                blob, blob_off = ops.pack_frames(out)
+                sink.append(blob.cpu().numpy(), blob_off.numpy())
+            else:
+                sink.append(out.cpu().numpy())
+        done += n_win
+
+    with torch.cuda.device(device):
+        for pos in range(0, len(payload), raw_chunk_bytes):
+            n = min(raw_chunk_bytes, len(payload) - pos)
+            pin_np[:n] = payload[pos:pos + n]
+            rec, state = ops.decode_evt(pin[:n].to(device, non_blocking=True), encoding, state)
+            if int(state[12].item()):
+                raise ValueError(f'{what}: an event time lies outside [0, 2^32) microseconds after the shift by the first TIME_HIGH; '
+                                 'it does not fit a .dat record')
+            rec = torch.cat([carry, rec]) if carry.shape[0] else rec
+            if rec.shape[0] == 0:
+                continue
+            t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
+            bad = torch.nonzero(t[1:] < t[:-1])
+            if bad.numel():                                      # the carried records come first: a decrease across two chunks shows here
+                i = int(bad[0])
+                raise ValueError(f'{what}: timestamps decrease ({int(t[i])} -> {int(t[i + 1])}); a recording must be sorted in time')
+            t_last = int(t[-1])
+            k_last = max(-(-t_last // D) - 1, 0)                  # the window of the last event: everything before it is complete
+            if k_last > done:
+                edges = torch.arange(done + 1, k_last + 1, dtype=torch.int64, device=device) * D
+                off = torch.cat([torch.zeros((1,), dtype=torch.int64, device=device), torch.searchsorted(t, edges, right=True)])
+                emit(rec, off)
+                carry = rec[int(off[-1]):].clone()
+            else:
+                carry = rec
+        n_frames = dat_events.num_windows(t_last, D)
+        assert n_frames == done + 1
+        emit(carry, torch.tensor([0, carry.shape[0]], dtype=torch.int64, device=device))
+        counters = ops.evt_state_counters(state) if state is not None else dict(events=0, early_events=0, ignored_words=0,
+                                                                                unknown_words=0, overflow=0, wraps=0)
+    return dict(frames=n_frames, dropped_events=int(dropped.item()), **counters)
+
+
+def _ingest_raw(raw_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes) -> Dict:
+    from leod_amd.data.utils import raw_events
+    ds2 = dataset_type == DatasetType.GEN4
+    hdr, payload = raw_events.open_words(raw_fn)
+    height, width = SENSOR_HW[dataset_type]
+    for name, got, want in (('height', hdr.height, height), ('width', hdr.width, width)):
+        if got is not None and got != want:
+            raise ValueError(f'{raw_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
+    if keep_classes is None:
+        keep_classes = DEFAULT_KEEP_CLASSES[dataset_type]
+    ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
+    os.makedirs(ev_dir, exist_ok=True)
+    os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
+    frame_fn = os.path.join(ev_dir, 'event_representations' + ('_ds2_nearest' if ds2 else '') + ('.npy' if write == 'npy' else '.evp'))
+    frame_shape = (2 * bins,) + ((height // 2, width // 2) if ds2 else (height, width))
+    if write == 'packed':
+        from leod_amd.data.utils.packed import PackedWriter
+        sink = PackedWriter(frame_fn, *frame_shape)
+    else:
+        sink = _NpyStream(frame_fn, frame_shape)
+    try:
+        res = voxelize_raw_recording(payload, hdr.encoding, sink, write == 'packed', duration_us, bins, height, width, ds2, raw_fn,
+                                     raw_chunk_bytes=raw_chunk_bytes)
+    except BaseException:
+        sink.abort()
+        raise
+    sink.close()
+    boxes = np.load(bbox_fn) if bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
+    labels, label_idx, repr_idx = convert_labels(boxes, res['frames'], duration_us, keep_classes)
+    np.save(os.path.join(ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
+    np.savez(os.path.join(out_dir, 'labels_v2', 'labels.npz'), labels=labels, objframe_idx_2_label_idx=label_idx)
+    return dict(recording=out_dir, frames=res['frames'], events=res['events'], dropped_events=res['dropped_events'],
+                labelled_frames=int(len(repr_idx)), boxes=int(len(labels)), early_events=res['early_events'],
+                ignored_words=res['ignored_words'], unknown_words=res['unknown_words'], clock_wraps=res['wraps'])
+
+
+def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
+                     keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', raw_chunk_bytes: int = RAW_CHUNK_BYTES) -> Dict:
     """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
     ``event_representations_ds2_nearest.npy`` at half resolution for Gen4) or, with ``write='packed'``, as the packed store of the same
     stem (``.evp``), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
-    ``keep_classes`` None: every class for Gen1, (0, 1, 2) for Gen4.  -> a small report."""
+    ``keep_classes`` None: every class for Gen1, (0, 1, 2) for Gen4.  -> a small report.
+    ``dat_fn`` may be a Metavision ``.raw`` file (EVT2 / EVT3): its payload is decoded on the device, ``raw_chunk_bytes`` at a time, and
+    the report also counts ``early_events``, ``ignored_words``, ``unknown_words`` and ``clock_wraps``.  ``bbox_fn`` None: an unlabelled
+    recording, the tree is written with zero labels."""
     if write not in ('npy', 'packed'):
         raise ValueError(f"write={write!r}: the raw 'npy' frame file or the 'packed' store is written (an HDF5 writer is not part of "
                          'this package)')
     dataset_type = _dataset_type(dataset_type)
+    if dat_fn.lower().endswith('.raw'):
+        return _ingest_raw(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes)
     ds2 = dataset_type == DatasetType.GEN4
     hdr, records = dat_events.open_records(dat_fn)
     height, width = SENSOR_HW[dataset_type]
@@ -140,7 +306,8 @@ def ingest_recording(dat_fn: str, bbox_fn: str, out_dir: str, dataset_type, dura
     n_frames = len(offsets) - 1
     if keep_classes is None:
         keep_classes = DEFAULT_KEEP_CLASSES[dataset_type]
-    labels, label_idx, repr_idx = convert_labels(np.load(bbox_fn), n_frames, duration_us, keep_classes)
+    boxes = np.load(bbox_fn) if bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
+    labels, label_idx, repr_idx = convert_labels(boxes, n_frames, duration_us, keep_classes)
 
     ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
     os.makedirs(ev_dir, exist_ok=True)
@@ -171,16 +338,29 @@ def ingest_recording(dat_fn: str, bbox_fn: str, out_dir: str, dataset_type, dura
 
 
 def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
-                 keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False):
-    """Every ``<name>_td.dat`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  -> the reports, in name order."""
+                 keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False, unlabelled: str = 'error',
+                 raw_chunk_bytes: int = RAW_CHUNK_BYTES):
+    """Every ``<name>_td.dat`` and every ``<name>.raw`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  A recording
+    without a box file raises ``FileNotFoundError`` (``unlabelled='error'``) or is written with zero labels (``'ok'``); the same name in
+    both containers is a ``ValueError``.  -> the reports, in file-name order."""
+    if unlabelled not in ('error', 'ok'):
+        raise ValueError(f"unlabelled={unlabelled!r}: 'error' or 'ok' expected")
+    found = {}
+    for fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat')) + glob.glob(os.path.join(src_dir, '*.raw'))):
+        base = os.path.basename(fn)
+        stem = base[:-len('_td.dat')] if base.endswith('_td.dat') else base[:-len('.raw')]
+        if stem in found:
+            raise ValueError(f'{src_dir}: the recording {stem!r} is there twice, as {os.path.basename(found[stem])} and as {base}')
+        found[stem] = fn
     reports = []
-    for dat_fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat'))):
-        stem = os.path.basename(dat_fn)[:-len('_td.dat')]
+    for stem, ev_fn in found.items():                            # in file-name order, as the .dat files always were
         bbox_fn = os.path.join(src_dir, stem + '_bbox.npy')
         if not os.path.exists(bbox_fn):
-            raise FileNotFoundError(f'{dat_fn} has no box file {bbox_fn}')
-        rep = ingest_recording(dat_fn, bbox_fn, os.path.join(dst_dir, stem), dataset_type, duration_us=duration_us, bins=bins,
-                               keep_classes=keep_classes, write=write)
+            if unlabelled == 'error':
+                raise FileNotFoundError(f'{ev_fn} has no box file {bbox_fn}')
+            bbox_fn = None
+        rep = ingest_recording(ev_fn, bbox_fn, os.path.join(dst_dir, stem), dataset_type, duration_us=duration_us, bins=bins,
+                               keep_classes=keep_classes, write=write, raw_chunk_bytes=raw_chunk_bytes)
         if verbose:
             print(rep, flush=True)
         reports.append(rep)
@@ -189,22 +369,24 @@ def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog='python -m leod_amd.data.ingest', description=__doc__.split('\n\n')[0])
-    ap.add_argument('src', help="directory of *_td.dat + *_bbox.npy pairs, or one that holds such directories named train / val / test")
+    ap.add_argument('src', help="directory of *_td.dat / *.raw recordings + *_bbox.npy, or one that holds such directories named train / val / test")
     ap.add_argument('dst', help='dataset path to write (dst/<split>/<recording>/...)')
     ap.add_argument('--dataset', required=True, choices=['gen1', 'gen4'])
     ap.add_argument('--duration-us', type=int, default=50_000)
     ap.add_argument('--bins', type=int, default=10)
     ap.add_argument('--keep-classes', type=int, nargs='*', default=None)
     ap.add_argument('--write', choices=['npy', 'packed'], default='npy', help="frame file: the raw .npy twin or the packed .evp store")
+    ap.add_argument('--unlabelled', choices=['error', 'ok'], default='error',
+                    help="a recording without a box file: an error, or a tree with zero labels (for pseudo-labelling)")
     args = ap.parse_args(argv)
     splits = [s for s in ('train', 'val', 'test') if os.path.isdir(os.path.join(args.src, s))]
     pairs = [(os.path.join(args.src, s), os.path.join(args.dst, s)) for s in splits] or [(args.src, args.dst)]
     n = 0
     for src, dst in pairs:
         n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
-                              write=args.write, verbose=True))
+                              write=args.write, verbose=True, unlabelled=args.unlabelled))
     if n == 0:
-        ap.error(f'no *_td.dat under {args.src}')
+        ap.error(f'no *_td.dat or *.raw under {args.src}')
     return 0
 
 

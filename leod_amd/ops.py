@@ -1630,6 +1630,67 @@ def voxelize_dat_windows(records_u8, win_off, bins, height, width, ds2=False, co
     return out, dropped
 
 
+EVT_FORMATS = {'evt2': 2, 'evt3': 3, 2: 2, 3: 3}
+EVT_WORD_BYTES = {2: 4, 3: 2}
+EVT_STATE_LONGS = 16
+_EVT_COUNTERS = dict(events=8, early_events=9, ignored_words=10, unknown_words=11, overflow=12, wraps=2)
+
+
+def evt_query(n_words: int = 0):
+    """(words per tile, tile summaries per pass of the scan workgroup, workspace bytes for a chunk of ``n_words`` words): the decoder's own
+    constants (csrc/k_evt.hip)."""
+    tw, tp, ws = (ctypes.c_int * 1)(), (ctypes.c_int * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_evt_query(int(n_words), tw, tp, ws), 'evt_query')
+    return int(tw[0]), int(tp[0]), int(ws[0])
+
+
+def decode_evt(words_u8, fmt, state=None, out=None):
+    """A chunk of a Metavision RAW payload on the device (uint8, as it lies in the file: EVT2 u32 words or EVT3 u16 words, whole words)
+    -> (records uint8 [n, 8], state).  The records are those of a .dat file (``voxelize_dat_windows`` reads them), in stream order.
+    ``state`` (int64 [16] on the device, layout in include/leod_hip.h) carries the decoder from chunk to chunk: None starts a recording;
+    the given tensor is not modified, the returned one is new.  ``out``: a contiguous device uint8 buffer to store the records in; it must
+    hold them all (its first n * 8 bytes are returned as the view [n, 8], nothing behind them is written).  Three launches and one
+    read-back (the chunk's event count)."""
+    if fmt not in EVT_FORMATS or isinstance(fmt, bool):
+        raise LeodHipError(f'encoding {fmt!r}: evt2 or evt3 expected')
+    fmt = EVT_FORMATS[fmt]
+    _ck(words_u8, torch.uint8, 'words')
+    if words_u8.numel() % EVT_WORD_BYTES[fmt]:
+        raise LeodHipError(f'words: {words_u8.numel()} bytes are no whole number of {EVT_WORD_BYTES[fmt]}-byte words')
+    dev = words_u8.device
+    if words_u8.data_ptr() % 16:
+        words_u8 = words_u8.clone()                              # the kernels load 16 bytes at a time; a fresh allocation is aligned
+    n_words = words_u8.numel() // EVT_WORD_BYTES[fmt]
+    if state is None:
+        state = torch.zeros((EVT_STATE_LONGS,), dtype=torch.int64, device=dev)
+    _ck(state, torch.int64, 'state')
+    if state.numel() != EVT_STATE_LONGS:
+        raise LeodHipError(f'state: {EVT_STATE_LONGS} int64 expected, got {tuple(state.shape)}')
+    ws_bytes = evt_query(n_words)[2]
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    new = torch.empty_like(state)
+    check(_l().leod_evt_scan(_p(words_u8), n_words, fmt, _p(state), _p(new), _p(ws), ws_bytes, _stream()), 'decode_evt (scan)')
+    n = int(new[14].item())
+    if out is None:
+        buf = torch.empty((n, 8), dtype=torch.uint8, device=dev)
+    else:
+        _ck(out, torch.uint8, 'out')
+        if out.numel() < n * 8:
+            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {n} records of the chunk')
+        if out.data_ptr() % 8:
+            raise LeodHipError('out: an 8-byte aligned buffer expected')
+        buf = out.reshape(-1)[:n * 8].view(n, 8)
+    check(_l().leod_evt_emit(_p(words_u8), n_words, fmt, _p(ws), ws_bytes, _p(buf), n, _p(new), _stream()), 'decode_evt (emit)')
+    return buf, new
+
+
+def evt_state_counters(state):
+    """The counters of a decoder state (one read-back): events, early_events, ignored_words, unknown_words, overflow, wraps."""
+    _ck(state, torch.int64, 'state')
+    host = state.cpu().tolist()
+    return {k: int(host[i]) for k, i in _EVT_COUNTERS.items()}
+
+
 def unpack_frames(blob_u8, slot_off, slot_flags, C, H, W, out=None):
     """Packed event frames (``data/utils/packed.py``) -> dense uint8 [n_slots, C, H, W] in one launch.  ``blob_u8``: device uint8 buffer of
     validated frame blobs; ``slot_off`` device int64 [n_slots]: byte offset (multiple of 16) of the blob each output frame decodes, < 0 for a
