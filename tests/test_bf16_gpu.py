@@ -307,6 +307,7 @@ STEM_ROUTE_CASES_16 = [
 
 @pytest.mark.parametrize('case', CONV_ROUTE_CASES_16 + STEM_ROUTE_CASES_16, ids=lambda c: '-'.join(str(v) for v in c[-1]) + '@' + 'x'.join(str(v) for v in c[:5]))
 def test_conv_every_route_16bit(bf16_ops, case):
+    """Gaussian operands at the 16-bit tolerance; tests/test_conv_exact_gpu.py runs the same rows on exact operands and asserts equality."""
     (tk.check_conv_routes if len(case) == 10 else tk.check_stem_routes)(bf16_ops, *case)
 
 

@@ -513,6 +513,7 @@ STEM_ROUTE_CASES_F32 = [
 
 @pytest.mark.parametrize('case', CONV_ROUTE_CASES_F32 + STEM_ROUTE_CASES_F32, ids=lambda c: '-'.join(str(v) for v in c[-1]) + '@' + 'x'.join(str(v) for v in c[:5]))
 def test_conv_every_route(ops, case):
+    """Gaussian operands at a tolerance; tests/test_conv_exact_gpu.py runs the same rows on exact operands and asserts equality."""
     (check_conv_routes if len(case) == 10 else check_stem_routes)(ops, *case)
 
 
