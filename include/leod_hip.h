@@ -552,6 +552,31 @@ int leod_evt_scan(const void* words, long n_words, int fmt, const long* state_in
                   leod_stream_t stream);
 int leod_evt_emit(const void* words, long n_words, int fmt, const void* ws, long ws_bytes, void* out, long capacity, long* state_out,
                   leod_stream_t stream);
+/* Event noise filters (csrc/k_filter.hip; the rule: DESIGN.md section 1) on the 8-byte .dat records above, in stream order, t
+ * non-decreasing.  An event with x >= W or y >= H is removed (outside); one on a pixel with mask[y * W + x] != 0 is removed (masked; mask
+ * may be NULL); any other is kept iff an earlier event that passed these two tests lies on one of its 8 neighbour pixels, at most tau_us
+ * before it (0 <= tau_us < 2^31), else it is removed (unsupported) -- and still supports later events; tau_us = -1 switches this third
+ * test off.  At most 2^31 - 1 events per call.
+ * state: 8 + H * W longs on the device, updated in place, carried from chunk to chunk: [0] seen [1] kept [2] outside [3] masked
+ *   [4] unsupported [5] time of the last event seen (-1: none) [6] [7] 0; then the surface [H, W]: the last time per pixel (-1: never).
+ *   A recording starts from zero counters and -1 everywhere else.
+ * io: 4 longs on the device: [0] records kept by this call so far (in: 0; sizes the output) [1] position of the first event whose time
+ *   is below that of the event before it (in: the largest long; stays so for a sorted chunk) [2] [3] the two times around it.
+ * leod_event_filter_query (host only): *tile_events = records per tile of the compaction, *tiles_per_pass = tile counts the scan workgroup
+ *   takes per pass, *table_bytes = the table that takes n_events records in one piece, *marks_bytes = the marks of a chunk of n_events.
+ * leod_event_filter_scan: decides every record of the chunk; table (16-byte aligned): table_bytes of scratch, at least 1024 -- a chunk
+ *   that needs more than it holds is cut at record boundaries into pieces of whole tiles that fit (that takes 8192 bytes or more), one
+ *   memset and four launches each; marks (8-byte aligned) receives the chunk's decisions.
+ * leod_event_filter_emit: same records, same marks; stores the kept records in order (out: 8-byte aligned, capacity in records; nothing
+ *   is stored at or beyond capacity), one launch.
+ * leod_event_pixel_counts: counts[y * W + x] += 1 for every event inside the sensor, *outside += the others (both on the device).
+ * -1 for bad arguments. */
+int leod_event_filter_query(long n_events, int* tile_events, int* tiles_per_pass, long* table_bytes, long* marks_bytes);
+int leod_event_filter_scan(const void* records, long n_events, int H, int W, long tau_us, const unsigned char* mask, long* state,
+                           void* table, long table_bytes, void* marks, long marks_bytes, long* io, leod_stream_t stream);
+int leod_event_filter_emit(const void* records, long n_events, const void* marks, long marks_bytes, void* out, long capacity,
+                           leod_stream_t stream);
+int leod_event_pixel_counts(const void* records, long n_events, int H, int W, long* counts, long* outside, leod_stream_t stream);
 
 /* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
  * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,

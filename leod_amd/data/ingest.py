@@ -17,7 +17,14 @@ A ``.raw`` file (EVT2 / EVT3; ``data/utils/raw_events.py``) goes to the device a
 (csrc/k_evt.hip) turns each chunk into the same 8-byte records, which then take the path above window by window.  ``--unlabelled ok``
 accepts recordings without a box file (trees with zero labels, to be pseudo-labelled).
 
+Noise filters (off by default; the rule: DESIGN.md section 1; ``ops.filter_events``, csrc/k_filter.hip): ``--pixel-mask FILE.npy`` removes
+the events of the masked pixels, ``--hot-rate HZ`` first counts the recording's events per pixel on the device and masks the pixels that
+fire faster (the mask is written beside the frames as ``hot_pixels.npy``), ``--denoise-us N`` keeps an event only if one of its 8
+neighbours fired at most N microseconds before it.  With one of them given, both containers take the streaming route of the ``.raw``
+files, at sensor resolution; the number of frames, the window edges and the label files are those of the unfiltered recording.
+
     python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed] [--unlabelled error|ok]
+                                   [--denoise-us N] [--pixel-mask FILE.npy] [--hot-rate HZ]
 """
 import argparse
 import glob
@@ -179,23 +186,33 @@ class _NpyStream:
 
 def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: bool, duration_us: int, bins: int, height: int, width: int,
                            ds2: bool, what: str, device=None, raw_chunk_bytes: int = RAW_CHUNK_BYTES,
-                           frames_per_copy: int = FRAMES_PER_COPY) -> Dict:
+                           frames_per_copy: int = FRAMES_PER_COPY, event_filter: Optional[Dict] = None) -> Dict:
     """Memory-mapped payload bytes of a .raw file -> frames appended to ``sink`` (``_NpyStream`` or, with ``packed``, a ``PackedWriter``).
     ``raw_chunk_bytes`` of payload at a time go through one pinned buffer and are decoded with the carried state (``ops.decode_evt``);
     sortedness and the window offsets of the decoded times are found on the device; every window that is complete -- a later event has
     been seen -- is voxelised by ``ops.voxelize_dat_windows``, the records of the last, incomplete one are carried into the next chunk.
-    -> dict(frames, dropped_events and the decoder's counters)."""
+    ``event_filter`` (dict(tau_us: int or None, mask: uint8 [H, W] or None)): every chunk's records go through ``ops.filter_events`` with
+    the carried filter state before they join the carry; the filter then checks the order of the times, and the windows are still cut at
+    the times of the events SEEN (one more small read-back per chunk): a window that loses all its events is a zero frame.  With it
+    ``encoding`` may be 'dat': ``payload`` is the bytes of .dat records, which need no decoder.
+    -> dict(frames, dropped_events and the decoder's counters; with a filter also kept_events, masked_events, unsupported_events)."""
     import torch
     from leod_amd import ops
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     raw_chunk_bytes = int(raw_chunk_bytes)
     if raw_chunk_bytes < 4 or raw_chunk_bytes % 4:
         raise ValueError(f'raw_chunk_bytes={raw_chunk_bytes}: a positive multiple of 4 expected')
+    if encoding == 'dat':
+        assert event_filter is not None, 'unfiltered .dat records take voxelize_recording'
+        raw_chunk_bytes = max(raw_chunk_bytes // 8, 1) * 8       # whole records
     D = int(duration_us)
     pin = torch.empty((min(raw_chunk_bytes, max(len(payload), 4)),), dtype=torch.uint8).pin_memory()
     pin_np = pin.numpy()
     dropped = torch.zeros((1,), dtype=torch.int64, device=device)
     state, carry, done, t_last = None, torch.empty((0, 8), dtype=torch.uint8, device=device), 0, 0
+    fstate, fmask = None, None
+    if event_filter is not None and event_filter.get('mask') is not None:
+        fmask = torch.from_numpy(np.ascontiguousarray(event_filter['mask'], dtype=np.uint8)).to(device)
 
     def emit(rec, off):                                          # windows `done` .. of rec, offsets [k + 1] on the device
         nonlocal done, dropped
@@ -216,19 +233,36 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
         for pos in range(0, len(payload), raw_chunk_bytes):
             n = min(raw_chunk_bytes, len(payload) - pos)
             pin_np[:n] = payload[pos:pos + n]
-            rec, state = ops.decode_evt(pin[:n].to(device, non_blocking=True), encoding, state)
-            if int(state[12].item()):
-                raise ValueError(f'{what}: an event time lies outside [0, 2^32) microseconds after the shift by the first TIME_HIGH; '
-                                 'it does not fit a .dat record')
-            rec = torch.cat([carry, rec]) if carry.shape[0] else rec
-            if rec.shape[0] == 0:
-                continue
-            t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
-            bad = torch.nonzero(t[1:] < t[:-1])
-            if bad.numel():                                      # the carried records come first: a decrease across two chunks shows here
-                i = int(bad[0])
-                raise ValueError(f'{what}: timestamps decrease ({int(t[i])} -> {int(t[i + 1])}); a recording must be sorted in time')
-            t_last = int(t[-1])
+            if encoding == 'dat':
+                rec = pin[:n].to(device, non_blocking=True).view(-1, 8)
+            else:
+                rec, state = ops.decode_evt(pin[:n].to(device, non_blocking=True), encoding, state)
+                if int(state[12].item()):
+                    raise ValueError(f'{what}: an event time lies outside [0, 2^32) microseconds after the shift by the first TIME_HIGH; '
+                                     'it does not fit a .dat record')
+            if event_filter is not None:
+                if rec.shape[0] == 0:
+                    continue
+                # The time of the last event SEEN, kept or not: it sets the number of frames.  This read-back is one more host
+                # synchronisation per chunk besides the op's own (the kept count), and for 'dat' it is also the FENCE behind the
+                # non-blocking copy out of the pinned buffer, which the next chunk overwrites (for .raw, decode_evt's read-back is).
+                t_last = int(rec.view(torch.int32)[-1, 0]) & 0xffffffff
+                try:
+                    rec, fstate = ops.filter_events(rec, height, width, event_filter.get('tau_us'), state=fstate, pixel_mask=fmask)
+                except ops.EventOrderError as e:
+                    raise ValueError(f'{what}: timestamps decrease ({e.t_before} -> {e.t_at}); a recording must be sorted in time') from None
+                rec = torch.cat([carry, rec]) if carry.shape[0] else rec
+                t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
+            else:
+                rec = torch.cat([carry, rec]) if carry.shape[0] else rec
+                if rec.shape[0] == 0:
+                    continue
+                t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
+                bad = torch.nonzero(t[1:] < t[:-1])
+                if bad.numel():                                  # the carried records come first: a decrease across two chunks shows here
+                    i = int(bad[0])
+                    raise ValueError(f'{what}: timestamps decrease ({int(t[i])} -> {int(t[i + 1])}); a recording must be sorted in time')
+                t_last = int(t[-1])
             k_last = max(-(-t_last // D) - 1, 0)                  # the window of the last event: everything before it is complete
             if k_last > done:
                 edges = torch.arange(done + 1, k_last + 1, dtype=torch.int64, device=device) * D
@@ -242,19 +276,108 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
         emit(carry, torch.tensor([0, carry.shape[0]], dtype=torch.int64, device=device))
         counters = ops.evt_state_counters(state) if state is not None else dict(events=0, early_events=0, ignored_words=0,
                                                                                 unknown_words=0, overflow=0, wraps=0)
+        if event_filter is not None:
+            fc = ops.event_filter_counters(fstate) if fstate is not None else dict(seen=0, kept=0, outside=0, masked=0, unsupported=0)
+            # the filter removes and counts the events outside the sensor: none is left for the voxeliser to drop
+            return dict(frames=n_frames, dropped_events=int(dropped.item()) + fc['outside'], kept_events=fc['kept'],
+                        masked_events=fc['masked'], unsupported_events=fc['unsupported'], **dict(counters, events=fc['seen']))
     return dict(frames=n_frames, dropped_events=int(dropped.item()), **counters)
 
 
-def _ingest_raw(raw_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes) -> Dict:
-    from leod_amd.data.utils import raw_events
+def count_pixel_events(payload: np.ndarray, encoding: str, height: int, width: int, what: str, device=None,
+                       raw_chunk_bytes: int = RAW_CHUNK_BYTES) -> Dict:
+    """The first pass of ``--hot-rate``: events per pixel of a whole recording, counted on the device (``ops.event_pixel_counts``) from the
+    payload of a .raw file (decoded a chunk at a time, as ``voxelize_raw_recording`` does) or the bytes of .dat records (``encoding``
+    'dat').  -> dict(counts int64 [H, W], outside, events, t_first, t_last): the times of the first and the last event (0 without any)."""
+    import torch
+    from leod_amd import ops
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    raw_chunk_bytes = int(raw_chunk_bytes)
+    if raw_chunk_bytes < 4 or raw_chunk_bytes % 4:
+        raise ValueError(f'raw_chunk_bytes={raw_chunk_bytes}: a positive multiple of 4 expected')
+    if encoding == 'dat':
+        raw_chunk_bytes = max(raw_chunk_bytes // 8, 1) * 8
+    pin = torch.empty((min(raw_chunk_bytes, max(len(payload), 4)),), dtype=torch.uint8).pin_memory()
+    pin_np = pin.numpy()
+    counts = torch.zeros((height, width), dtype=torch.int64, device=device)
+    outside = torch.zeros((1,), dtype=torch.int64, device=device)
+    state, first, last, events = None, None, None, 0
+    with torch.cuda.device(device):
+        for pos in range(0, len(payload), raw_chunk_bytes):
+            n = min(raw_chunk_bytes, len(payload) - pos)
+            pin_np[:n] = payload[pos:pos + n]
+            if encoding == 'dat':
+                rec = pin[:n].to(device, non_blocking=True).view(-1, 8)
+            else:
+                rec, state = ops.decode_evt(pin[:n].to(device, non_blocking=True), encoding, state)
+            if rec.shape[0] == 0:
+                continue
+            events += rec.shape[0]
+            if first is None:
+                first = rec[0].clone()
+            last = rec[-1].clone()
+            _, o = ops.event_pixel_counts(rec, height, width, counts)
+            outside += o
+            torch.cuda.current_stream().synchronize()           # the pinned buffer is reused by the next chunk
+        t_first = int(first.view(torch.int32)[0]) & 0xffffffff if first is not None else 0
+        t_last = int(last.view(torch.int32)[0]) & 0xffffffff if last is not None else 0
+        if state is not None and int(state[12].item()):
+            raise ValueError(f'{what}: an event time lies outside [0, 2^32) microseconds after the shift by the first TIME_HIGH; '
+                             'it does not fit a .dat record')
+        return dict(counts=counts.cpu().numpy(), outside=int(outside.item()), events=events, t_first=t_first, t_last=t_last)
+
+
+def check_filter_options(dataset_type, denoise_us=None, pixel_mask=None, hot_rate_hz=None) -> Optional[Dict]:
+    """The three filter options of a call, checked on the host before anything is opened -> None when all are off, else
+    dict(tau_us, mask, hot_rate_hz): ``pixel_mask`` (a ``.npy`` file name or an array) read and checked against the sensor of the
+    dataset."""
+    from leod_amd.data.utils import event_filter as ef
+    if denoise_us is None and pixel_mask is None and hot_rate_hz is None:
+        return None
+    if denoise_us is not None:
+        if isinstance(denoise_us, (bool, float)) or int(denoise_us) != denoise_us or not 0 <= int(denoise_us) < 2 ** 31:
+            raise ValueError(f'denoise_us={denoise_us!r}: an integer number of microseconds in [0, 2^31) expected')
+        denoise_us = int(denoise_us)
+    if hot_rate_hz is not None:
+        if isinstance(hot_rate_hz, (bool, float)) or int(hot_rate_hz) != hot_rate_hz or int(hot_rate_hz) < 0:
+            raise ValueError(f'hot_rate_hz={hot_rate_hz!r}: a non-negative integer rate in events per second expected')
+        hot_rate_hz = int(hot_rate_hz)
+    sensor = SENSOR_HW[_dataset_type(dataset_type)]
+    mask = None
+    if pixel_mask is not None:
+        mask = ef.read_pixel_mask(pixel_mask, sensor) if isinstance(pixel_mask, (str, os.PathLike)) else ef.check_pixel_mask(pixel_mask, sensor)
+    return dict(tau_us=denoise_us, mask=mask, hot_rate_hz=hot_rate_hz)
+
+
+def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt=None) -> Dict:
+    """A recording through ``voxelize_raw_recording``: a ``.raw`` file (``flt`` None: as it always was), or, with a noise filter on
+    (``flt`` of ``check_filter_options``), a ``.raw`` or a ``.dat`` file."""
     ds2 = dataset_type == DatasetType.GEN4
-    hdr, payload = raw_events.open_words(raw_fn)
+    is_raw = ev_fn.lower().endswith('.raw')
+    if is_raw:
+        from leod_amd.data.utils import raw_events
+        hdr, payload = raw_events.open_words(ev_fn)
+        encoding, sizes = hdr.encoding, (('height', hdr.height), ('width', hdr.width))
+    else:
+        assert flt is not None, 'an unfiltered .dat recording takes voxelize_recording'
+        hdr, records = dat_events.open_records(ev_fn)
+        payload = records.view(np.uint8).reshape(-1)
+        encoding, sizes = 'dat', (('Height', hdr.height), ('Width', hdr.width))
     height, width = SENSOR_HW[dataset_type]
-    for name, got, want in (('height', hdr.height, height), ('width', hdr.width, width)):
+    for (name, got), want in zip(sizes, (height, width)):
         if got is not None and got != want:
-            raise ValueError(f'{raw_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
+            raise ValueError(f'{ev_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
     if keep_classes is None:
         keep_classes = DEFAULT_KEEP_CLASSES[dataset_type]
+    event_filter = mask = None
+    if flt is not None:
+        mask = flt['mask']
+        if flt['hot_rate_hz'] is not None:
+            from leod_amd.data.utils import event_filter as ef
+            seen = count_pixel_events(payload, encoding, height, width, ev_fn, raw_chunk_bytes=raw_chunk_bytes)
+            hot = ef.hot_pixel_mask(seen['counts'], max(seen['t_last'] - seen['t_first'], 1), flt['hot_rate_hz'])
+            mask = hot if mask is None else (mask | hot)
+        event_filter = dict(tau_us=flt['tau_us'], mask=mask)
     ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
     os.makedirs(ev_dir, exist_ok=True)
     os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
@@ -266,36 +389,53 @@ def _ingest_raw(raw_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_
     else:
         sink = _NpyStream(frame_fn, frame_shape)
     try:
-        res = voxelize_raw_recording(payload, hdr.encoding, sink, write == 'packed', duration_us, bins, height, width, ds2, raw_fn,
-                                     raw_chunk_bytes=raw_chunk_bytes)
+        res = voxelize_raw_recording(payload, encoding, sink, write == 'packed', duration_us, bins, height, width, ds2, ev_fn,
+                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter)
     except BaseException:
         sink.abort()
         raise
     sink.close()
+    if flt is not None and flt['hot_rate_hz'] is not None:
+        from leod_amd.data.utils import event_filter as ef
+        np.save(os.path.join(ev_dir, ef.MASK_FILE), mask)        # the mask that was applied: --pixel-mask with it repeats the run
     boxes = np.load(bbox_fn) if bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
     labels, label_idx, repr_idx = convert_labels(boxes, res['frames'], duration_us, keep_classes)
     np.save(os.path.join(ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
     np.savez(os.path.join(out_dir, 'labels_v2', 'labels.npz'), labels=labels, objframe_idx_2_label_idx=label_idx)
-    return dict(recording=out_dir, frames=res['frames'], events=res['events'], dropped_events=res['dropped_events'],
-                labelled_frames=int(len(repr_idx)), boxes=int(len(labels)), early_events=res['early_events'],
-                ignored_words=res['ignored_words'], unknown_words=res['unknown_words'], clock_wraps=res['wraps'])
+    rep = dict(recording=out_dir, frames=res['frames'], events=res['events'], dropped_events=res['dropped_events'],
+               labelled_frames=int(len(repr_idx)), boxes=int(len(labels)))
+    if is_raw:
+        rep.update(early_events=res['early_events'], ignored_words=res['ignored_words'], unknown_words=res['unknown_words'],
+                   clock_wraps=res['wraps'])
+    if flt is not None:
+        rep.update(kept_events=res['kept_events'], masked_events=res['masked_events'], unsupported_events=res['unsupported_events'],
+                   masked_pixels=int(np.count_nonzero(mask)) if mask is not None else 0)
+    return rep
 
 
 def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
-                     keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', raw_chunk_bytes: int = RAW_CHUNK_BYTES) -> Dict:
+                     keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', raw_chunk_bytes: int = RAW_CHUNK_BYTES,
+                     denoise_us: Optional[int] = None, pixel_mask=None, hot_rate_hz: Optional[int] = None) -> Dict:
     """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
     ``event_representations_ds2_nearest.npy`` at half resolution for Gen4) or, with ``write='packed'``, as the packed store of the same
     stem (``.evp``), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
     ``keep_classes`` None: every class for Gen1, (0, 1, 2) for Gen4.  -> a small report.
     ``dat_fn`` may be a Metavision ``.raw`` file (EVT2 / EVT3): its payload is decoded on the device, ``raw_chunk_bytes`` at a time, and
     the report also counts ``early_events``, ``ignored_words``, ``unknown_words`` and ``clock_wraps``.  ``bbox_fn`` None: an unlabelled
-    recording, the tree is written with zero labels."""
+    recording, the tree is written with zero labels.
+    Noise filters (all off by default, and then nothing here differs): ``denoise_us`` keeps an event only if one of its 8 neighbours
+    fired at most so many microseconds before it; ``pixel_mask`` (a ``.npy`` file or a uint8 / bool array [H, W] at sensor resolution)
+    removes the events of its non-zero pixels; ``hot_rate_hz`` counts the recording's events per pixel in a first pass and masks the pixels
+    above that rate (OR-ed with ``pixel_mask``; written beside the frames as ``hot_pixels.npy``).  The frames, the window edges and the
+    labels stay those of the unfiltered recording; the report gains ``kept_events``, ``masked_events``, ``unsupported_events`` and
+    ``masked_pixels``, and ``dropped_events`` is the filter's count of events outside the sensor."""
     if write not in ('npy', 'packed'):
         raise ValueError(f"write={write!r}: the raw 'npy' frame file or the 'packed' store is written (an HDF5 writer is not part of "
                          'this package)')
     dataset_type = _dataset_type(dataset_type)
-    if dat_fn.lower().endswith('.raw'):
-        return _ingest_raw(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes)
+    flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
+    if flt is not None or dat_fn.lower().endswith('.raw'):
+        return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt)
     ds2 = dataset_type == DatasetType.GEN4
     hdr, records = dat_events.open_records(dat_fn)
     height, width = SENSOR_HW[dataset_type]
@@ -339,12 +479,16 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
 
 def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
                  keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False, unlabelled: str = 'error',
-                 raw_chunk_bytes: int = RAW_CHUNK_BYTES):
+                 raw_chunk_bytes: int = RAW_CHUNK_BYTES, denoise_us: Optional[int] = None, pixel_mask=None,
+                 hot_rate_hz: Optional[int] = None):
     """Every ``<name>_td.dat`` and every ``<name>.raw`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  A recording
     without a box file raises ``FileNotFoundError`` (``unlabelled='error'``) or is written with zero labels (``'ok'``); the same name in
-    both containers is a ``ValueError``.  -> the reports, in file-name order."""
+    both containers is a ``ValueError``.  ``denoise_us``, ``pixel_mask``, ``hot_rate_hz``: the noise filters of ``ingest_recording``, the same
+    for every recording (a mask file is read once).  -> the reports, in file-name order."""
     if unlabelled not in ('error', 'ok'):
         raise ValueError(f"unlabelled={unlabelled!r}: 'error' or 'ok' expected")
+    flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
+    filter_kw = {} if flt is None else dict(denoise_us=flt['tau_us'], pixel_mask=flt['mask'], hot_rate_hz=flt['hot_rate_hz'])
     found = {}
     for fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat')) + glob.glob(os.path.join(src_dir, '*.raw'))):
         base = os.path.basename(fn)
@@ -360,7 +504,7 @@ def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50
                 raise FileNotFoundError(f'{ev_fn} has no box file {bbox_fn}')
             bbox_fn = None
         rep = ingest_recording(ev_fn, bbox_fn, os.path.join(dst_dir, stem), dataset_type, duration_us=duration_us, bins=bins,
-                               keep_classes=keep_classes, write=write, raw_chunk_bytes=raw_chunk_bytes)
+                               keep_classes=keep_classes, write=write, raw_chunk_bytes=raw_chunk_bytes, **filter_kw)
         if verbose:
             print(rep, flush=True)
         reports.append(rep)
@@ -378,13 +522,25 @@ def main(argv=None) -> int:
     ap.add_argument('--write', choices=['npy', 'packed'], default='npy', help="frame file: the raw .npy twin or the packed .evp store")
     ap.add_argument('--unlabelled', choices=['error', 'ok'], default='error',
                     help="a recording without a box file: an error, or a tree with zero labels (for pseudo-labelling)")
+    ap.add_argument('--denoise-us', type=int, default=None, metavar='N',
+                    help='keep an event only if one of its 8 neighbour pixels fired at most N microseconds before it')
+    ap.add_argument('--pixel-mask', default=None, metavar='FILE.npy',
+                    help='uint8 / bool array [H, W] at sensor resolution; the events of its non-zero pixels are removed')
+    ap.add_argument('--hot-rate', type=int, default=None, metavar='HZ',
+                    help='first count the events per pixel of each recording and mask the pixels that fire faster than HZ events/s '
+                         '(the mask is written beside the frames as hot_pixels.npy)')
     args = ap.parse_args(argv)
+    try:
+        check_filter_options(args.dataset, args.denoise_us, args.pixel_mask, args.hot_rate)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
     splits = [s for s in ('train', 'val', 'test') if os.path.isdir(os.path.join(args.src, s))]
     pairs = [(os.path.join(args.src, s), os.path.join(args.dst, s)) for s in splits] or [(args.src, args.dst)]
     n = 0
     for src, dst in pairs:
         n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
-                              write=args.write, verbose=True, unlabelled=args.unlabelled))
+                              write=args.write, verbose=True, unlabelled=args.unlabelled, denoise_us=args.denoise_us,
+                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate))
     if n == 0:
         ap.error(f'no *_td.dat or *.raw under {args.src}')
     return 0

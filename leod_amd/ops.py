@@ -1691,6 +1691,136 @@ def evt_state_counters(state):
     return {k: int(host[i]) for k, i in _EVT_COUNTERS.items()}
 
 
+# scratch of one piece of a chunk of ``filter_events`` (the (slot, pixel) table of csrc/k_filter.hip): 64 MiB takes 2^21 records in one
+# piece.  Sweep in DESIGN.md section 4 (profiles/r11_a_kbench_filter.txt, SYNTHETIC recording): 1 MiB is 5x slower, 16 MiB 13 %, 32 MiB 5 %;
+# 64 MiB is within 4 % of the fastest bound (256 MiB, a whole 64 MiB chunk of records in one piece) at a quarter of its memory
+FILTER_WS_BYTES = 64 << 20
+FILTER_WS_MIN_BYTES = 8192       # the smallest table that still takes a whole tile of records per piece
+FILTER_STATE_HEAD = 8
+FILTER_TAU_LIMIT = 1 << 31
+_FILTER_COUNTERS = dict(seen=0, kept=1, outside=2, masked=3, unsupported=4)
+_LONG_MAX = (1 << 63) - 1
+
+
+class EventOrderError(LeodHipError):
+    """A chunk of records whose times decrease: ``position`` of the first event that is earlier than the one before it (0: earlier than
+    the last event of the chunk before), and the two times."""
+
+    def __init__(self, position: int, t_before: int, t_at: int):
+        super().__init__(f'records: timestamps decrease at event {position} ({t_before} -> {t_at}); a recording must be sorted in time')
+        self.position, self.t_before, self.t_at = position, t_before, t_at
+
+
+def event_filter_query(n_events: int = 0):
+    """(records per tile, tile counts per pass of the scan workgroup, table bytes that take ``n_events`` records in one piece, bytes of
+    marks for a chunk of ``n_events``): the filter's own constants (csrc/k_filter.hip)."""
+    te, tp, tb, mb = (ctypes.c_int * 1)(), (ctypes.c_int * 1)(), (ctypes.c_long * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_event_filter_query(int(n_events), te, tp, tb, mb), 'event_filter_query')
+    return int(te[0]), int(tp[0]), int(tb[0]), int(mb[0])
+
+
+def _ck_records(records_u8):
+    _ck(records_u8, torch.uint8, 'records')
+    if records_u8.numel() % 8:
+        raise LeodHipError(f'records: {records_u8.numel()} bytes are no whole number of 8-byte events')
+    if records_u8.data_ptr() % 8:
+        records_u8 = records_u8.clone()                          # the kernels load a record at a time; a fresh allocation is aligned
+    return records_u8, records_u8.numel() // 8
+
+
+def _ck_sensor(height, width):
+    for name, v in (('height', height), ('width', width)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384:
+            raise LeodHipError(f'{name}={v!r}: an integer in [1, 16384] expected')
+
+
+def filter_events(records_u8, height, width, tau_us, state=None, pixel_mask=None, out=None, ws_bytes=None):
+    """A chunk of .dat records on the device (uint8 [n * 8] or [n, 8], stream order, t non-decreasing) -> (kept records uint8 [m, 8],
+    state) by the rule of DESIGN.md section 1: events outside [0, W) x [0, H) and events on a pixel where ``pixel_mask`` (uint8 or bool
+    [H, W] on the device) is non-zero are removed; any other is kept iff an earlier such event lies on one of its 8 neighbours at most
+    ``tau_us`` before it (0 <= tau_us < 2^31; None: this third rule is off).  Kept records come out unchanged and in order.
+    ``state`` (int64 [8 + H * W] on the device, layout in include/leod_hip.h: five counters, the last time seen, the last time per pixel)
+    carries the filter from chunk to chunk: None starts a recording; the given tensor is not modified, the returned one is new.  ``out``:
+    a contiguous device uint8 buffer to store the records in; it must hold them all (its first m * 8 bytes are returned as the view
+    [m, 8], nothing behind them is written).  A chunk whose times decrease -- against the chunk before, too -- raises
+    ``EventOrderError``.  ``ws_bytes`` (None: ``FILTER_WS_BYTES``) bounds the table: a chunk that needs more is cut into pieces that fit,
+    which changes nothing but the launches.  One memset and four launches per piece, one launch to emit, one read-back (the kept count)."""
+    _ck_sensor(height, width)
+    if tau_us is not None and (isinstance(tau_us, bool) or not isinstance(tau_us, int) or not 0 <= tau_us < FILTER_TAU_LIMIT):
+        raise LeodHipError(f'tau_us={tau_us!r}: an integer in [0, 2^31) expected (None: bounds and mask only)')
+    records_u8, n = _ck_records(records_u8)
+    dev = records_u8.device
+    if n >= 1 << 31:
+        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
+    if pixel_mask is not None:
+        if not isinstance(pixel_mask, torch.Tensor) or pixel_mask.dtype not in (torch.uint8, torch.bool):
+            raise LeodHipError(f'pixel_mask: a uint8 or bool tensor expected, got {getattr(pixel_mask, "dtype", type(pixel_mask))}')
+        _ck(pixel_mask, pixel_mask.dtype, 'pixel_mask')
+        if tuple(pixel_mask.shape) != (height, width):
+            raise LeodHipError(f'pixel_mask: shape {tuple(pixel_mask.shape)}, the sensor is {(height, width)}')
+    n_state = FILTER_STATE_HEAD + height * width
+    if state is None:
+        new = torch.full((n_state,), -1, dtype=torch.int64, device=dev)
+        new[:FILTER_STATE_HEAD] = torch.tensor([0, 0, 0, 0, 0, -1, 0, 0], dtype=torch.int64)
+    else:
+        _ck(state, torch.int64, 'state')
+        if state.numel() != n_state:
+            raise LeodHipError(f'state: {n_state} int64 expected for a {height} x {width} sensor, got {tuple(state.shape)}')
+        new = state.clone()
+    ws_bytes = FILTER_WS_BYTES if ws_bytes is None else int(ws_bytes)
+    if ws_bytes < FILTER_WS_MIN_BYTES:
+        raise LeodHipError(f'ws_bytes={ws_bytes}: at least {FILTER_WS_MIN_BYTES} expected')
+    _, _, table_bytes, marks_bytes = event_filter_query(n)
+    table_bytes = min(table_bytes, ws_bytes)
+    table = torch.empty((max(table_bytes, 16) // 8,), dtype=torch.int64, device=dev)
+    marks = torch.empty((max(marks_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(dev)
+    check(_l().leod_event_filter_scan(_p(records_u8), n, height, width, -1 if tau_us is None else tau_us, _p(pixel_mask), _p(new), _p(table), table_bytes,
+                                       _p(marks), marks_bytes, _p(io), _stream()), 'filter_events (scan)')
+    m, bad, t_before, t_at = io.cpu().tolist()
+    if bad != _LONG_MAX:
+        raise EventOrderError(bad, t_before, t_at)
+    if out is None:
+        buf = torch.empty((m, 8), dtype=torch.uint8, device=dev)
+    else:
+        _ck(out, torch.uint8, 'out')
+        if out.numel() < m * 8:
+            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {m} records the filter keeps')
+        if out.data_ptr() % 8:
+            raise LeodHipError('out: an 8-byte aligned buffer expected')
+        buf = out.reshape(-1)[:m * 8].view(m, 8)
+    check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), 'filter_events (emit)')
+    return buf, new
+
+
+def event_filter_counters(state):
+    """The counters of a filter state (one read-back): seen, kept, outside, masked, unsupported."""
+    _ck(state, torch.int64, 'state')
+    if state.numel() < FILTER_STATE_HEAD:
+        raise LeodHipError(f'state: a filter state expected, got {tuple(state.shape)}')
+    host = state[:FILTER_STATE_HEAD].cpu().tolist()
+    return {k: int(host[i]) for k, i in _FILTER_COUNTERS.items()}
+
+
+def event_pixel_counts(records_u8, height, width, counts=None):
+    """Events per pixel of a chunk of .dat records on the device, added into ``counts`` (int64 [H, W] on the device; None: a new one of
+    zeros) -> (counts, outside): ``outside`` (int64 [1] on the device) is the number of events with x >= W or y >= H, which are skipped.
+    One launch, no read-back."""
+    _ck_sensor(height, width)
+    records_u8, n = _ck_records(records_u8)
+    dev = records_u8.device
+    if n >= 1 << 31:
+        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
+    if counts is None:
+        counts = torch.zeros((height, width), dtype=torch.int64, device=dev)
+    _ck(counts, torch.int64, 'counts')
+    if tuple(counts.shape) != (height, width):
+        raise LeodHipError(f'counts: shape {tuple(counts.shape)}, the sensor is {(height, width)}')
+    outside = torch.zeros((1,), dtype=torch.int64, device=dev)
+    check(_l().leod_event_pixel_counts(_p(records_u8), n, height, width, _p(counts), _p(outside), _stream()), 'event_pixel_counts')
+    return counts, outside
+
+
 def unpack_frames(blob_u8, slot_off, slot_flags, C, H, W, out=None):
     """Packed event frames (``data/utils/packed.py``) -> dense uint8 [n_slots, C, H, W] in one launch.  ``blob_u8``: device uint8 buffer of
     validated frame blobs; ``slot_off`` device int64 [n_slots]: byte offset (multiple of 16) of the blob each output frame decodes, < 0 for a
