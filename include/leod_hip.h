@@ -577,6 +577,32 @@ int leod_event_filter_scan(const void* records, long n_events, int H, int W, lon
 int leod_event_filter_emit(const void* records, long n_events, const void* marks, long marks_bytes, void* out, long capacity,
                            leod_stream_t stream);
 int leod_event_pixel_counts(const void* records, long n_events, int H, int W, long* counts, long* outside, leod_stream_t stream);
+/* Per-pixel event filters (csrc/k_pixfilter.hip; the rule: DESIGN.md section 1) on the same records, in stream order, t non-decreasing:
+ * bounds and mask as above (outside, masked; such events touch no state); any other event is a candidate and updates its pixel's state,
+ * whatever its verdict.  burst_us (-1: off; else 0 <= burst_us < 2^31): a candidate continues the burst of the candidate before it on
+ * its pixel when the polarity is the same and it lies at most burst_us behind it; its position k is counted 1, 2, 3 (= 3 or later);
+ * burst_keep 0 keeps k = 1 (trail), 1 keeps k = 2, 2 keeps k >= 2 (STC); the others are removed (burst).  lock (0: off; else 1..255) with
+ * 1 <= p_min_us <= p_max_us < 2^31: a rising edge is an ON candidate that is the pixel's first or follows an OFF one; n_per counts
+ * consecutive periods between rising edges within [p_min_us, p_max_us], saturates at lock, and is reset by a period outside the band or
+ * by any candidate later than p_max_us behind the last edge; while n_per >= lock every candidate of the pixel is removed (flicker,
+ * which is tested before burst).  At most 2^31 - 1 events per call.
+ * state: 8 + 4 * H * W longs on the device, updated in place, carried from chunk to chunk: [0] seen [1] kept [2] outside [3] masked
+ *   [4] flicker [5] burst [6] time of the last event seen (-1: none) [7] 0; then per pixel q at 8 + 4 * q: t_prev (time of the last
+ *   candidate; -1: never), t_edge (time of the last rising edge; -1: none), p_prev + 2 * k_prev, n_per.  A recording starts from zero
+ *   counters, [6] = -1 and {-1, -1, 0, 0} in every pixel.
+ * io: as for leod_event_filter_scan.
+ * leod_pixel_filter_query (host only): *tile_events = records per tile (of the sort and of the compaction), *tiles_per_pass = tile counts
+ *   the scan workgroup takes per pass, *digit_bits = key bits per pass of the sort (ceil(ceil(log2(H * W)) / digit_bits) passes),
+ *   *ws_bytes = the workspace that takes n_events records in one piece, *marks_bytes = the marks of a chunk of n_events (any may be NULL).
+ * leod_pixel_filter_scan: decides every record of the chunk; ws (8-byte aligned): ws_bytes of scratch -- a chunk that needs more than it
+ *   holds is cut at record boundaries into pieces of whole tiles that fit (the workspace of one tile, leod_pixel_filter_query(1, ...), is
+ *   the least); marks (8-byte aligned) receives the chunk's decisions in the layout leod_event_filter_emit reads, which stores the kept
+ *   records.  -1 for bad arguments. */
+int leod_pixel_filter_query(long n_events, int H, int W, int* tile_events, int* tiles_per_pass, int* digit_bits, long* ws_bytes,
+                            long* marks_bytes);
+int leod_pixel_filter_scan(const void* records, long n_events, int H, int W, long burst_us, int burst_keep, long p_min_us, long p_max_us,
+                           int lock, const unsigned char* mask, long* state, void* ws, long ws_bytes, void* marks, long marks_bytes,
+                           long* io, leod_stream_t stream);
 
 /* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
  * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,

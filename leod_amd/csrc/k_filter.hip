@@ -24,18 +24,14 @@
 // indexed through `& (capacity - 1)` and a probe sequence ends after `capacity` steps at the latest (records crafted to collide cost
 // time, never an access outside the table); a record is stored only at a
 // position below `capacity`; the entry points refuse buffers smaller than leod_event_filter_query reports.
-#include "common.hpp"
+#include "filter_common.hpp"
 
 namespace {
-constexpr int BLOCK = 256;
-constexpr int TILE = BLOCK;                                      // one record per lane
-constexpr int PASS = BLOCK;                                      // tile counts per pass of the scan workgroup
+using namespace filt;                                            // Rec, BLOCK / TILE / PASS, the io block, the sums: filter_common.hpp
 constexpr long MIN_ENTRIES = 64;
-enum { C_KEPT = 0, C_OUTSIDE = 1, C_MASKED = 2, C_UNSUPPORTED = 3 };
+enum { C_OUTSIDE = 1, C_MASKED = 2, C_UNSUPPORTED = 3 };         // C_KEPT = 0
 enum { S_SEEN = 0, S_KEPT, S_OUTSIDE, S_MASKED, S_UNSUPPORTED, S_T_LAST, S_HEAD = 8 };      // state block: include/leod_hip.h
-enum { IO_EMITTED = 0, IO_BAD, IO_T_BEFORE, IO_T_AT };
 
-struct Rec { unsigned t, xyp; };
 struct Entry { unsigned long long key; unsigned fneg, m; };      // key 0: empty; fneg = ~(smallest record index); m = largest time
 
 __device__ __forceinline__ unsigned long long make_key(unsigned slot, int x, int y) {
@@ -69,32 +65,6 @@ __device__ __forceinline__ const Entry* table_find(const Entry* tab, unsigned lo
         h = (h + 1) & (cap - 1);
     }
     return nullptr;
-}
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// exclusive prefix sum over the workgroup's lanes + the total; every lane must call it
-__device__ __forceinline__ unsigned long long block_scan_sum(unsigned long long mine, unsigned long long& total, unsigned long long* lds /* [4] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long q = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += q;
-    }
-    __syncthreads();                                             // the previous use of lds is over
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0;
-    total = 0;
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w < wave) before += lds[w];
-        total += lds[w];
-    }
-    return before + inc - mine;
 }
 
 // (a) records [lo, hi): class, insert of the candidates, first position where the time decreases
@@ -233,13 +203,6 @@ long table_entries(long n_events) {                              // a power of t
     long cap = MIN_ENTRIES;
     while (cap < 2 * n_events) cap <<= 1;
     return cap;
-}
-long marks_need(long n_events) {                                 // class bytes, padded to 8, + one u64 per tile
-    return (n_events + 7) / 8 * 8 + (n_events + TILE - 1) / TILE * 8L;
-}
-bool records_ok(const void* records, long n_events) {
-    if (n_events < 0 || n_events > 0x7fffffffL) return false;
-    return n_events == 0 || (records && (reinterpret_cast<uintptr_t>(records) & 7) == 0);
 }
 }  // namespace
 

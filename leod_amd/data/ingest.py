@@ -23,8 +23,15 @@ fire faster (the mask is written beside the frames as ``hot_pixels.npy``), ``--d
 neighbours fired at most N microseconds before it.  With one of them given, both containers take the streaming route of the ``.raw``
 files, at sensor resolution; the number of frames, the window edges and the label files are those of the unfiltered recording.
 
+Per-pixel filters (off by default; the rule: DESIGN.md section 1; ``ops.pixel_filter_events``, csrc/k_pixfilter.hip): ``--trail-us N`` keeps
+the first event of every burst of same-polarity events of a pixel that follow each other within N microseconds, ``--stc-us N`` keeps a
+burst from its second event on (``--stc-cut-trail``: the second alone), ``--anti-flicker FMIN:FMAX`` removes the events of a pixel
+whose rising edges have repeated ``--flicker-lock`` times in a row at a frequency in the band.  They run first, on whole per-pixel
+sequences, and apply the bounds and the mask; ``--denoise-us`` then sees what they keep.
+
     python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed] [--unlabelled error|ok]
                                    [--denoise-us N] [--pixel-mask FILE.npy] [--hot-rate HZ]
+                                   [--trail-us N | --stc-us N [--stc-cut-trail]] [--anti-flicker FMIN:FMAX [--flicker-lock N]]
 """
 import argparse
 import glob
@@ -194,7 +201,10 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
     ``event_filter`` (dict(tau_us: int or None, mask: uint8 [H, W] or None)): every chunk's records go through ``ops.filter_events`` with
     the carried filter state before they join the carry; the filter then checks the order of the times, and the windows are still cut at
     the times of the events SEEN (one more small read-back per chunk): a window that loses all its events is a zero frame.  With it
-    ``encoding`` may be 'dat': ``payload`` is the bytes of .dat records, which need no decoder.
+    ``encoding`` may be 'dat': ``payload`` is the bytes of .dat records, which need no decoder.  With ``event_filter['pixel']``
+    (dict(burst_us, burst_keep, flicker) of ``check_pixel_filter_options``) the records first go through ``ops.pixel_filter_events``,
+    which applies the bounds and the mask and needs whole per-pixel sequences; ``ops.filter_events`` follows only where ``tau_us`` is
+    set, and the report also holds flicker_events and burst_events.
     -> dict(frames, dropped_events and the decoder's counters; with a filter also kept_events, masked_events, unsupported_events)."""
     import torch
     from leod_amd import ops
@@ -211,6 +221,7 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
     dropped = torch.zeros((1,), dtype=torch.int64, device=device)
     state, carry, done, t_last = None, torch.empty((0, 8), dtype=torch.uint8, device=device), 0, 0
     fstate, fmask = None, None
+    pixel, pstate = (event_filter or {}).get('pixel'), None
     if event_filter is not None and event_filter.get('mask') is not None:
         fmask = torch.from_numpy(np.ascontiguousarray(event_filter['mask'], dtype=np.uint8)).to(device)
 
@@ -248,7 +259,12 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
                 # non-blocking copy out of the pinned buffer, which the next chunk overwrites (for .raw, decode_evt's read-back is).
                 t_last = int(rec.view(torch.int32)[-1, 0]) & 0xffffffff
                 try:
-                    rec, fstate = ops.filter_events(rec, height, width, event_filter.get('tau_us'), state=fstate, pixel_mask=fmask)
+                    if pixel is not None:
+                        rec, pstate = ops.pixel_filter_events(rec, height, width, state=pstate, pixel_mask=fmask, **pixel)
+                        if event_filter.get('tau_us') is not None and rec.shape[0]:          # bounds and mask are applied already
+                            rec, fstate = ops.filter_events(rec, height, width, event_filter['tau_us'], state=fstate)
+                    else:
+                        rec, fstate = ops.filter_events(rec, height, width, event_filter.get('tau_us'), state=fstate, pixel_mask=fmask)
                 except ops.EventOrderError as e:
                     raise ValueError(f'{what}: timestamps decrease ({e.t_before} -> {e.t_at}); a recording must be sorted in time') from None
                 rec = torch.cat([carry, rec]) if carry.shape[0] else rec
@@ -278,6 +294,13 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
                                                                                 unknown_words=0, overflow=0, wraps=0)
         if event_filter is not None:
             fc = ops.event_filter_counters(fstate) if fstate is not None else dict(seen=0, kept=0, outside=0, masked=0, unsupported=0)
+            if pixel is not None:                                # the first stage saw every event; the second one its output
+                pc = ops.pixel_filter_counters(pstate) if pstate is not None else dict(seen=0, kept=0, outside=0, masked=0, flicker=0,
+                                                                                       burst=0)
+                kept = fc['kept'] if event_filter.get('tau_us') is not None else pc['kept']
+                return dict(frames=n_frames, dropped_events=int(dropped.item()) + pc['outside'], kept_events=kept,
+                            masked_events=pc['masked'], unsupported_events=fc['unsupported'], flicker_events=pc['flicker'],
+                            burst_events=pc['burst'], **dict(counters, events=pc['seen']))
             # the filter removes and counts the events outside the sensor: none is left for the voxeliser to drop
             return dict(frames=n_frames, dropped_events=int(dropped.item()) + fc['outside'], kept_events=fc['kept'],
                         masked_events=fc['masked'], unsupported_events=fc['unsupported'], **dict(counters, events=fc['seen']))
@@ -349,9 +372,43 @@ def check_filter_options(dataset_type, denoise_us=None, pixel_mask=None, hot_rat
     return dict(tau_us=denoise_us, mask=mask, hot_rate_hz=hot_rate_hz)
 
 
-def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt=None) -> Dict:
-    """A recording through ``voxelize_raw_recording``: a ``.raw`` file (``flt`` None: as it always was), or, with a noise filter on
-    (``flt`` of ``check_filter_options``), a ``.raw`` or a ``.dat`` file."""
+def check_pixel_filter_options(trail_us=None, stc_us=None, stc_cut_trail=False, anti_flicker=None, flicker_lock=None) -> Optional[Dict]:
+    """The per-pixel filter options of a call, checked on the host before anything is opened -> None when all are off, else the keyword
+    arguments of ``ops.pixel_filter_events``: dict(burst_us, burst_keep, flicker).  ``trail_us`` keeps the first event of a burst,
+    ``stc_us`` a burst from its second event on (``stc_cut_trail``: the second alone); ``anti_flicker``: 'FMIN:FMAX' or (fmin, fmax) in
+    Hz, ``flicker_lock`` (None: 3) the in-band periods in a row after which a pixel is removed."""
+    from leod_amd.data.utils import event_filter as ef
+    if trail_us is not None and stc_us is not None:
+        raise ValueError('trail_us and stc_us: one burst rule at a time (a trail filter keeps the first event of a burst, STC drops it)')
+    if stc_cut_trail not in (False, True):
+        raise ValueError(f'stc_cut_trail={stc_cut_trail!r}: True or False expected')
+    if stc_cut_trail and stc_us is None:
+        raise ValueError('stc_cut_trail needs stc_us')
+    if flicker_lock is not None and anti_flicker is None:
+        raise ValueError('flicker_lock needs anti_flicker')
+    burst_us, burst_keep = None, 'first'
+    for name, v in (('trail_us', trail_us), ('stc_us', stc_us)):
+        if v is None:
+            continue
+        if isinstance(v, (bool, float)) or int(v) != v or not 0 <= int(v) < 2 ** 31:
+            raise ValueError(f'{name}={v!r}: an integer number of microseconds in [0, 2^31) expected')
+        burst_us = int(v)
+        burst_keep = 'first' if name == 'trail_us' else ('second' if stc_cut_trail else 'from_second')
+    flicker = None
+    if anti_flicker is not None:
+        lock = ef.DEFAULT_FLICKER_LOCK if flicker_lock is None else flicker_lock
+        if isinstance(lock, (bool, float)) or int(lock) != lock or not 1 <= int(lock) <= 255:
+            raise ValueError(f'flicker_lock={flicker_lock!r}: an integer in [1, 255] expected')
+        flicker = ef.flicker_band(anti_flicker) + (int(lock),)
+    if burst_us is None and flicker is None:
+        return None
+    return dict(burst_us=burst_us, burst_keep=burst_keep, flicker=flicker)
+
+
+def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt=None,
+                      pix=None) -> Dict:
+    """A recording through ``voxelize_raw_recording``: a ``.raw`` file (``flt`` and ``pix`` None: as it always was), or, with a noise
+    filter on (``flt`` of ``check_filter_options``, ``pix`` of ``check_pixel_filter_options``), a ``.raw`` or a ``.dat`` file."""
     ds2 = dataset_type == DatasetType.GEN4
     is_raw = ev_fn.lower().endswith('.raw')
     if is_raw:
@@ -359,7 +416,7 @@ def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, 
         hdr, payload = raw_events.open_words(ev_fn)
         encoding, sizes = hdr.encoding, (('height', hdr.height), ('width', hdr.width))
     else:
-        assert flt is not None, 'an unfiltered .dat recording takes voxelize_recording'
+        assert flt is not None or pix is not None, 'an unfiltered .dat recording takes voxelize_recording'
         hdr, records = dat_events.open_records(ev_fn)
         payload = records.view(np.uint8).reshape(-1)
         encoding, sizes = 'dat', (('Height', hdr.height), ('Width', hdr.width))
@@ -378,6 +435,8 @@ def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, 
             hot = ef.hot_pixel_mask(seen['counts'], max(seen['t_last'] - seen['t_first'], 1), flt['hot_rate_hz'])
             mask = hot if mask is None else (mask | hot)
         event_filter = dict(tau_us=flt['tau_us'], mask=mask)
+    if pix is not None:
+        event_filter = dict(event_filter or dict(tau_us=None, mask=None), pixel=pix)
     ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
     os.makedirs(ev_dir, exist_ok=True)
     os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
@@ -407,15 +466,19 @@ def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, 
     if is_raw:
         rep.update(early_events=res['early_events'], ignored_words=res['ignored_words'], unknown_words=res['unknown_words'],
                    clock_wraps=res['wraps'])
-    if flt is not None:
+    if flt is not None or pix is not None:
         rep.update(kept_events=res['kept_events'], masked_events=res['masked_events'], unsupported_events=res['unsupported_events'],
                    masked_pixels=int(np.count_nonzero(mask)) if mask is not None else 0)
+    if pix is not None:
+        rep.update(flicker_events=res['flicker_events'], burst_events=res['burst_events'])
     return rep
 
 
 def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
                      keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', raw_chunk_bytes: int = RAW_CHUNK_BYTES,
-                     denoise_us: Optional[int] = None, pixel_mask=None, hot_rate_hz: Optional[int] = None) -> Dict:
+                     denoise_us: Optional[int] = None, pixel_mask=None, hot_rate_hz: Optional[int] = None,
+                     trail_us: Optional[int] = None, stc_us: Optional[int] = None, stc_cut_trail: bool = False, anti_flicker=None,
+                     flicker_lock: Optional[int] = None) -> Dict:
     """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
     ``event_representations_ds2_nearest.npy`` at half resolution for Gen4) or, with ``write='packed'``, as the packed store of the same
     stem (``.evp``), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
@@ -428,12 +491,18 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
     removes the events of its non-zero pixels; ``hot_rate_hz`` counts the recording's events per pixel in a first pass and masks the pixels
     above that rate (OR-ed with ``pixel_mask``; written beside the frames as ``hot_pixels.npy``).  The frames, the window edges and the
     labels stay those of the unfiltered recording; the report gains ``kept_events``, ``masked_events``, ``unsupported_events`` and
-    ``masked_pixels``, and ``dropped_events`` is the filter's count of events outside the sensor."""
+    ``masked_pixels``, and ``dropped_events`` is the filter's count of events outside the sensor.
+    Per-pixel filters (``check_pixel_filter_options``; all off by default, and then nothing here differs): ``trail_us`` / ``stc_us`` /
+    ``stc_cut_trail`` and ``anti_flicker`` / ``flicker_lock``.  They run first and apply the bounds and the mask, ``denoise_us`` then
+    sees what they keep; the report also gains ``flicker_events`` and ``burst_events``, ``kept_events`` is what reaches the voxeliser."""
     if write not in ('npy', 'packed'):
         raise ValueError(f"write={write!r}: the raw 'npy' frame file or the 'packed' store is written (an HDF5 writer is not part of "
                          'this package)')
     dataset_type = _dataset_type(dataset_type)
     flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
+    pix = check_pixel_filter_options(trail_us, stc_us, stc_cut_trail, anti_flicker, flicker_lock)
+    if pix is not None:
+        return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix)
     if flt is not None or dat_fn.lower().endswith('.raw'):
         return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt)
     ds2 = dataset_type == DatasetType.GEN4
@@ -480,15 +549,19 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
 def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,
                  keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False, unlabelled: str = 'error',
                  raw_chunk_bytes: int = RAW_CHUNK_BYTES, denoise_us: Optional[int] = None, pixel_mask=None,
-                 hot_rate_hz: Optional[int] = None):
+                 hot_rate_hz: Optional[int] = None, trail_us: Optional[int] = None, stc_us: Optional[int] = None,
+                 stc_cut_trail: bool = False, anti_flicker=None, flicker_lock: Optional[int] = None):
     """Every ``<name>_td.dat`` and every ``<name>.raw`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  A recording
     without a box file raises ``FileNotFoundError`` (``unlabelled='error'``) or is written with zero labels (``'ok'``); the same name in
     both containers is a ``ValueError``.  ``denoise_us``, ``pixel_mask``, ``hot_rate_hz``: the noise filters of ``ingest_recording``, the same
-    for every recording (a mask file is read once).  -> the reports, in file-name order."""
+    for every recording (a mask file is read once); ``trail_us``, ``stc_us``, ``stc_cut_trail``, ``anti_flicker``, ``flicker_lock``: its
+    per-pixel filters.  -> the reports, in file-name order."""
     if unlabelled not in ('error', 'ok'):
         raise ValueError(f"unlabelled={unlabelled!r}: 'error' or 'ok' expected")
     flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
     filter_kw = {} if flt is None else dict(denoise_us=flt['tau_us'], pixel_mask=flt['mask'], hot_rate_hz=flt['hot_rate_hz'])
+    if check_pixel_filter_options(trail_us, stc_us, stc_cut_trail, anti_flicker, flicker_lock) is not None:
+        filter_kw.update(trail_us=trail_us, stc_us=stc_us, stc_cut_trail=stc_cut_trail, anti_flicker=anti_flicker, flicker_lock=flicker_lock)
     found = {}
     for fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat')) + glob.glob(os.path.join(src_dir, '*.raw'))):
         base = os.path.basename(fn)
@@ -529,9 +602,22 @@ def main(argv=None) -> int:
     ap.add_argument('--hot-rate', type=int, default=None, metavar='HZ',
                     help='first count the events per pixel of each recording and mask the pixels that fire faster than HZ events/s '
                          '(the mask is written beside the frames as hot_pixels.npy)')
+    burst = ap.add_mutually_exclusive_group()
+    burst.add_argument('--trail-us', type=int, default=None, metavar='N',
+                       help='per pixel, keep only the first event of a burst of same-polarity events that follow each other within N microseconds')
+    burst.add_argument('--stc-us', type=int, default=None, metavar='N',
+                       help='per pixel, keep such a burst from its second event on: an event is confirmed by a second one')
+    ap.add_argument('--stc-cut-trail', action='store_true', help='with --stc-us: keep the second event of a burst alone')
+    ap.add_argument('--anti-flicker', default=None, metavar='FMIN:FMAX',
+                    help='remove the events of a pixel whose rising edges repeat at a frequency between FMIN and FMAX Hz (integers)')
+    ap.add_argument('--flicker-lock', type=int, default=None, metavar='N',
+                    help='in-band periods in a row after which a pixel counts as flickering (default 3)')
     args = ap.parse_args(argv)
+    pix_kw = dict(trail_us=args.trail_us, stc_us=args.stc_us, stc_cut_trail=args.stc_cut_trail, anti_flicker=args.anti_flicker,
+                  flicker_lock=args.flicker_lock)
     try:
         check_filter_options(args.dataset, args.denoise_us, args.pixel_mask, args.hot_rate)
+        check_pixel_filter_options(**pix_kw)
     except (ValueError, OSError) as e:
         ap.error(str(e))
     splits = [s for s in ('train', 'val', 'test') if os.path.isdir(os.path.join(args.src, s))]
@@ -540,7 +626,7 @@ def main(argv=None) -> int:
     for src, dst in pairs:
         n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
                               write=args.write, verbose=True, unlabelled=args.unlabelled, denoise_us=args.denoise_us,
-                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate))
+                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate, **pix_kw))
     if n == 0:
         ap.error(f'no *_td.dat or *.raw under {args.src}')
     return 0

@@ -1,10 +1,38 @@
-"""Host side of the event noise filters of the ingestion (``ops.filter_events``, csrc/k_filter.hip; the rule: DESIGN.md section 1): the
-hot-pixel threshold and the pixel-mask file.  NumPy only; nothing here touches the device."""
+"""Host side of the event noise filters of the ingestion (``ops.filter_events``, csrc/k_filter.hip; ``ops.pixel_filter_events``,
+csrc/k_pixfilter.hip; the rules: DESIGN.md section 1): the hot-pixel threshold, the pixel-mask file and the band of the anti-flicker
+filter.  NumPy only; nothing here touches the device."""
 from typing import Tuple
 
 import numpy as np
 
 MASK_FILE = 'hot_pixels.npy'         # written beside the frames when the mask was derived from the recording (--hot-rate)
+DEFAULT_FLICKER_LOCK = 3             # in-band periods in a row after which a pixel is removed; a default with no data behind it
+MAX_FLICKER_HZ = 1_000_000
+
+
+def flicker_band(band) -> Tuple[int, int]:
+    """'FMIN:FMAX' or (fmin, fmax), integer Hz with 1 <= FMIN <= FMAX <= 10^6 -> (p_min_us, p_max_us), the periods in whole microseconds
+    that lie in the band: p_min = ceil(10^6 / FMAX), p_max = floor(10^6 / FMIN).  ``ValueError`` where no whole period does (3:3)."""
+    if isinstance(band, str):
+        parts = band.split(':')
+        if len(parts) != 2 or not all(q.strip().isdigit() for q in parts):
+            raise ValueError(f'anti_flicker={band!r}: FMIN:FMAX in integer Hz expected')
+        fmin, fmax = (int(q) for q in parts)
+    else:
+        try:
+            fmin, fmax = band
+        except (TypeError, ValueError):
+            raise ValueError(f'anti_flicker={band!r}: FMIN:FMAX or a pair (fmin, fmax) in integer Hz expected') from None
+        for v in (fmin, fmax):
+            if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f'anti_flicker={band!r}: integer frequencies expected')
+        fmin, fmax = int(fmin), int(fmax)
+    if not 1 <= fmin <= fmax <= MAX_FLICKER_HZ:
+        raise ValueError(f'anti_flicker={band!r}: 1 <= FMIN <= FMAX <= {MAX_FLICKER_HZ} Hz expected')
+    p_min, p_max = -(-1_000_000 // fmax), 1_000_000 // fmin
+    if p_min > p_max:
+        raise ValueError(f'anti_flicker={band!r}: no whole number of microseconds is a period in this band')
+    return p_min, p_max
 
 
 def hot_pixel_mask(counts, duration_us: int, max_rate_hz: int) -> np.ndarray:

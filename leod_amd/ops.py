@@ -1802,6 +1802,120 @@ def event_filter_counters(state):
     return {k: int(host[i]) for k, i in _FILTER_COUNTERS.items()}
 
 
+# scratch of one piece of a chunk of ``pixel_filter_events`` (keys and indices of the sort of csrc/k_pixfilter.hip, twice, and its digit
+# counts: 16.5 bytes a record): 16 MiB takes a million records in one piece.  Sweep in DESIGN.md section 4
+# (profiles/r12_a_kbench_pixfilter.txt, SYNTHETIC recording): the fastest of 4, 16, 64 and 256 MiB, which lie within 18 % of each other
+PIXFILTER_WS_BYTES = 16 << 20
+PIXFILTER_STATE_HEAD = 8
+PIXFILTER_PIXEL_LONGS = 4
+PIXFILTER_KEEP = dict(first=0, second=1, from_second=2)
+_PIXFILTER_COUNTERS = dict(seen=0, kept=1, outside=2, masked=3, flicker=4, burst=5)
+
+
+def pixel_filter_query(n_events: int, height: int, width: int):
+    """(records per tile, tile counts per pass of the scan workgroup, key bits per pass of the sort, workspace bytes that take ``n_events``
+    records in one piece, bytes of marks for a chunk of ``n_events``): the per-pixel filter's own constants (csrc/k_pixfilter.hip)."""
+    _ck_sensor(height, width)
+    te, tp, db = (ctypes.c_int * 1)(), (ctypes.c_int * 1)(), (ctypes.c_int * 1)()
+    wb, mb = (ctypes.c_long * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_pixel_filter_query(int(n_events), height, width, te, tp, db, wb, mb), 'pixel_filter_query')
+    return int(te[0]), int(tp[0]), int(db[0]), int(wb[0]), int(mb[0])
+
+
+def _ck_flicker(flicker):
+    """None or (p_min_us, p_max_us, lock) -> (p_min, p_max, lock) for the C side (lock 0: off)."""
+    if flicker is None:
+        return 0, 0, 0
+    if not isinstance(flicker, (tuple, list)) or len(flicker) != 3 or \
+            any(isinstance(v, bool) or not isinstance(v, int) for v in flicker):
+        raise LeodHipError(f'flicker={flicker!r}: None or three integers (p_min_us, p_max_us, lock) expected')
+    p_min, p_max, lock = flicker
+    if not 1 <= p_min <= p_max < FILTER_TAU_LIMIT:
+        raise LeodHipError(f'flicker={flicker!r}: 1 <= p_min_us <= p_max_us < 2^31 expected')
+    if not 1 <= lock <= 255:
+        raise LeodHipError(f'flicker={flicker!r}: 1 <= lock <= 255 expected')
+    return p_min, p_max, lock
+
+
+def pixel_filter_events(records_u8, height, width, burst_us=None, burst_keep='first', flicker=None, state=None, pixel_mask=None, out=None,
+                        ws_bytes=None):
+    """A chunk of .dat records on the device (uint8 [n * 8] or [n, 8], stream order, t non-decreasing) -> (kept records uint8 [m, 8],
+    state) by the per-pixel rule of DESIGN.md section 1: events outside [0, W) x [0, H) and events on a pixel where ``pixel_mask`` (uint8
+    or bool [H, W] on the device) is non-zero are removed and touch no state; any other is a candidate.  ``burst_us`` (0 <= burst_us <
+    2^31; None: off): a candidate of the polarity of the candidate before it on its pixel, at most ``burst_us`` behind it, continues that
+    one's burst; ``burst_keep`` keeps the 'first' of every burst (trail filter), the 'second' alone, or all 'from_second' on (STC).
+    ``flicker`` (None: off; (p_min_us, p_max_us, lock) with 1 <= p_min_us <= p_max_us < 2^31, 1 <= lock <= 255): after ``lock``
+    consecutive periods between rising edges of a pixel inside the band, every event of the pixel is removed until a period misses the
+    band or an event comes later than p_max_us behind the last edge.  Kept records come out unchanged and in order.
+    ``state`` (int64 [8 + 4 * H * W] on the device, layout in include/leod_hip.h: six counters, the last time seen, four words per pixel)
+    carries the filter from chunk to chunk: None starts a recording; the given tensor is not modified, the returned one is new.  ``out``:
+    a contiguous device uint8 buffer to store the records in; it must hold them all (its first m * 8 bytes are returned as the view
+    [m, 8], nothing behind them is written).  A chunk whose times decrease -- against the chunk before, too -- raises
+    ``EventOrderError``.  ``ws_bytes`` (None: ``PIXFILTER_WS_BYTES``) bounds the workspace: a chunk that needs more is cut into pieces
+    that fit, which changes nothing but the launches.  Per piece four launches and three per pass of the sort, one launch to emit, one
+    read-back (the kept count and the order verdict)."""
+    _ck_sensor(height, width)
+    if burst_us is not None and (isinstance(burst_us, bool) or not isinstance(burst_us, int) or not 0 <= burst_us < FILTER_TAU_LIMIT):
+        raise LeodHipError(f'burst_us={burst_us!r}: an integer in [0, 2^31) expected (None: no burst rule)')
+    if not isinstance(burst_keep, str) or burst_keep not in PIXFILTER_KEEP:
+        raise LeodHipError(f"burst_keep={burst_keep!r}: 'first', 'second' or 'from_second' expected")
+    p_min, p_max, lock = _ck_flicker(flicker)
+    records_u8, n = _ck_records(records_u8)
+    dev = records_u8.device
+    if n >= 1 << 31:
+        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
+    if pixel_mask is not None:
+        if not isinstance(pixel_mask, torch.Tensor) or pixel_mask.dtype not in (torch.uint8, torch.bool):
+            raise LeodHipError(f'pixel_mask: a uint8 or bool tensor expected, got {getattr(pixel_mask, "dtype", type(pixel_mask))}')
+        _ck(pixel_mask, pixel_mask.dtype, 'pixel_mask')
+        if tuple(pixel_mask.shape) != (height, width):
+            raise LeodHipError(f'pixel_mask: shape {tuple(pixel_mask.shape)}, the sensor is {(height, width)}')
+    n_state = PIXFILTER_STATE_HEAD + PIXFILTER_PIXEL_LONGS * height * width
+    if state is None:
+        new = torch.tensor([-1, -1, 0, 0], dtype=torch.int64, device=dev).repeat(height * width + 2)
+        new[:PIXFILTER_STATE_HEAD] = torch.tensor([0, 0, 0, 0, 0, 0, -1, 0], dtype=torch.int64)
+    else:
+        _ck(state, torch.int64, 'state')
+        if state.numel() != n_state:
+            raise LeodHipError(f'state: {n_state} int64 expected for a {height} x {width} sensor, got {tuple(state.shape)}')
+        new = state.clone()
+    _, _, _, need, marks_bytes = pixel_filter_query(n, height, width)
+    least = pixel_filter_query(1, height, width)[3]
+    ws_bytes = PIXFILTER_WS_BYTES if ws_bytes is None else int(ws_bytes)
+    if ws_bytes < least:
+        raise LeodHipError(f'ws_bytes={ws_bytes}: at least {least} (one tile of records) expected')
+    ws_bytes = min(need, ws_bytes)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    marks = torch.empty((max(marks_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(dev)
+    check(_l().leod_pixel_filter_scan(_p(records_u8), n, height, width, -1 if burst_us is None else burst_us, PIXFILTER_KEEP[burst_keep],
+                                       p_min, p_max, lock, _p(pixel_mask), _p(new), _p(ws), ws_bytes, _p(marks), marks_bytes, _p(io),
+                                       _stream()), 'pixel_filter_events (scan)')
+    m, bad, t_before, t_at = io.cpu().tolist()
+    if bad != _LONG_MAX:
+        raise EventOrderError(bad, t_before, t_at)
+    if out is None:
+        buf = torch.empty((m, 8), dtype=torch.uint8, device=dev)
+    else:
+        _ck(out, torch.uint8, 'out')
+        if out.numel() < m * 8:
+            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {m} records the filter keeps')
+        if out.data_ptr() % 8:
+            raise LeodHipError('out: an 8-byte aligned buffer expected')
+        buf = out.reshape(-1)[:m * 8].view(m, 8)
+    check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), 'pixel_filter_events (emit)')
+    return buf, new
+
+
+def pixel_filter_counters(state):
+    """The counters of a per-pixel filter state (one read-back): seen, kept, outside, masked, flicker, burst."""
+    _ck(state, torch.int64, 'state')
+    if state.numel() < PIXFILTER_STATE_HEAD:
+        raise LeodHipError(f'state: a per-pixel filter state expected, got {tuple(state.shape)}')
+    host = state[:PIXFILTER_STATE_HEAD].cpu().tolist()
+    return {k: int(host[i]) for k, i in _PIXFILTER_COUNTERS.items()}
+
+
 def event_pixel_counts(records_u8, height, width, counts=None):
     """Events per pixel of a chunk of .dat records on the device, added into ``counts`` (int64 [H, W] on the device; None: a new one of
     zeros) -> (counts, outside): ``outside`` (int64 [1] on the device) is the number of events with x >= W or y >= H, which are skipped.
