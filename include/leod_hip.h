@@ -167,7 +167,9 @@ int leod_convlstm_seq_fwd(const float* xin, int x_is_projection, float* hbuf, fl
                           float* gates_out, const void* wpack, int M, int C, int T, int zero_state, int gates16, leod_stream_t stream);
 /* Backward through time of the same: dh_seq [T,M,C] (optional) gradients of every h_t from above, dc_last [M,C] (optional);
  * writes dgates_out [T,M,4C] (pre-activation; dx = dgates W_x and the weight gradient are one GEMM each over all T*M rows)
- * and optionally dh0 / dc0 [M,C].  LEOD_ERR_UNSUPPORTED (-3) when the weight slice does not fit the registers. */
+ * and optionally dh0 / dc0 [M,C].  gates [T,M,4,C] and cbuf [T+1,M,C] as the forward call wrote them; zero_state: c_0 is taken as zeros
+ * and slot 0 of cbuf is not read, on every route (slots 1..T are read; hbuf is not needed).  LEOD_ERR_UNSUPPORTED (-3) when the weight
+ * slice does not fit the registers. */
 int leod_convlstm_seq_bwd(const float* dh_seq, const float* dc_last, const float* gates, const float* cbuf, const float* W,
                           float* dgates_out, float* dh0, float* dc0, const void* wpack, int M, int C, int T, int zero_state,
                           int gates16, leod_stream_t stream);

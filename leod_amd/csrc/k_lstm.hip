@@ -459,7 +459,7 @@ template <int C, bool G16 = false>
 __global__ __launch_bounds__(C * 2) void lstm_seq_bwd_stream_kernel(const float* __restrict__ dh_seq, const float* __restrict__ dc_last,
                                                                      const float* __restrict__ gates, const float* __restrict__ cbuf,
                                                                      const s8v* __restrict__ wpb, float* __restrict__ dgates_out,
-                                                                     float* __restrict__ dh0, float* __restrict__ dc0, int M, int T) {
+                                                                     float* __restrict__ dh0, float* __restrict__ dc0, int M, int T, int zero_state) {
     constexpr int KA = 4 * C, KC = KA / 32, LD = KA + 16, NB = C >= 512 ? 2 : 4, NBT = KC / NB;
     static_assert(KC % NB == 0, "chunk batches");
     __shared__ __attribute__((aligned(16))) unsigned short sA[2][16 * LD];
@@ -487,6 +487,10 @@ __global__ __launch_bounds__(C * 2) void lstm_seq_bwd_stream_kernel(const float*
         asm volatile("" : "+s"(wb));                          // see the forward kernel: keeps the fragment loads inside the time loop
         const float* gp = gates + (long)t * M * 4 * C;
         const float* c0 = cbuf + (long)t * MC;
+        // zero_state: c_0 = 0 and slot 0 is not read (as in lstm_seq_bwd_kernel) -- the load goes to slot 1 instead, so that it stays one
+        // unconditional load next to its neighbours, and a wave-uniform select drops the value
+        const bool cz = zero_state && t == 0;
+        const float* cpp = cz ? c0 + MC : c0;
         float* dgp = dgates_out + (long)t * M * 4 * C;
 #pragma unroll
         for (int grp = 0; grp < 2; ++grp) {
@@ -500,7 +504,7 @@ __global__ __launch_bounds__(C * 2) void lstm_seq_bwd_stream_kernel(const float*
 #pragma unroll
                     for (int g = 0; g < 4; ++g) gg[g][r] = gr[g * C];
                 }
-                cpv[r] = c0[oc[grp][r]];
+                cpv[r] = cpp[oc[grp][r]];
                 ctv[r] = c0[MC + oc[grp][r]];
                 dhv[r] = dh_seq ? dh_seq[(long)t * MC + oc[grp][r]] : 0.f;
             }
@@ -510,7 +514,7 @@ __global__ __launch_bounds__(C * 2) void lstm_seq_bwd_stream_kernel(const float*
                 const float th = tanh_<true>(ctv[r]);
                 const float dh = dhv[r] + dhr[grp][r];
                 const float dc = dh * o * (1.0f - th * th) + dcn[grp][r];
-                const float d0 = dc * cpv[r] * f * (1.0f - f), d1 = dc * g * ig * (1.0f - ig);
+                const float d0 = dc * (cz ? 0.f : cpv[r]) * f * (1.0f - f), d1 = dc * g * ig * (1.0f - ig);
                 const float d2 = dh * th * o * (1.0f - o), d3 = dc * ig * (1.0f - g * g);
                 dcn[grp][r] = dc * f;
                 unsigned short* ar = &sA[buf][(4 * q + r) * LD + ch];
@@ -594,8 +598,8 @@ static int launch_lstm_seq_bwd(const LstmSeqBwdArgs& a, hipStream_t s) {
     const dim3 grid(cdiv(a.M, 16));
     if constexpr (FAM == 3) {
         const s8v* wpb = reinterpret_cast<const s8v*>(a.wpack) + (long)C * C / 2;
-        if (a.gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<C, true>), grid, dim3(C * 2), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, wpb, a.dgates_out, a.dh0, a.dc0, a.M, a.T);
-        else hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<C>), grid, dim3(C * 2), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, wpb, a.dgates_out, a.dh0, a.dc0, a.M, a.T);
+        if (a.gates16) hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<C, true>), grid, dim3(C * 2), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, wpb, a.dgates_out, a.dh0, a.dc0, a.M, a.T, a.zero_state);
+        else hipLaunchKernelGGL((lstm_seq_bwd_stream_kernel<C>), grid, dim3(C * 2), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, wpb, a.dgates_out, a.dh0, a.dc0, a.M, a.T, a.zero_state);
     } else if constexpr (FAM != 0) {
         if (BF && a.gates16) hipLaunchKernelGGL((lstm_seq_bwd_kernel<C, BF, BF>), grid, dim3(C * 4), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, a.W, a.dgates_out, a.dh0, a.dc0, a.M, a.T, a.zero_state);
         else hipLaunchKernelGGL((lstm_seq_bwd_kernel<C, BF>), grid, dim3(C * 4), 0, s, a.dh_seq, a.dc_last, a.gates, a.cbuf, a.W, a.dgates_out, a.dh0, a.dc0, a.M, a.T, a.zero_state);
