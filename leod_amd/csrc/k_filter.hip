@@ -27,9 +27,9 @@
 #include "filter_common.hpp"
 
 namespace {
-using namespace filt;                                            // Rec, BLOCK / TILE / PASS, the io block, the sums: filter_common.hpp
+using namespace filt;                 // Rec, BLOCK / TILE / PASS, the io block, the sums, classify / tally_classes / scan_tiles: filter_common.hpp
 constexpr long MIN_ENTRIES = 64;
-enum { C_OUTSIDE = 1, C_MASKED = 2, C_UNSUPPORTED = 3 };         // C_KEPT = 0
+enum { C_UNSUPPORTED = 3, N_CLASS = 4 };                         // behind C_KEPT, C_OUTSIDE, C_MASKED
 enum { S_SEEN = 0, S_KEPT, S_OUTSIDE, S_MASKED, S_UNSUPPORTED, S_T_LAST, S_HEAD = 8 };      // state block: include/leod_hip.h
 
 struct Entry { unsigned long long key; unsigned fneg, m; };      // key 0: empty; fneg = ~(smallest record index); m = largest time
@@ -74,13 +74,8 @@ __global__ __launch_bounds__(BLOCK) void filter_build_kernel(const Rec* __restri
                                                              unsigned char* __restrict__ cls, long* __restrict__ io) {
     const long i = lo + (long)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= hi) return;
-    const Rec e = rec[i];
-    const long before = i > 0 ? (long)rec[i - 1].t : state[S_T_LAST];             // -1: nothing seen yet
-    if ((long)e.t < before) atomicMin(reinterpret_cast<long long*>(io + IO_BAD), (long long)i);
-    const int x = (int)(e.xyp & 16383u), y = (int)((e.xyp >> 14) & 16383u);
-    int c = C_KEPT;
-    if (x >= W || y >= H) c = C_OUTSIDE;
-    else if (mask && mask[(long)y * W + x]) c = C_MASKED;
+    Rec e; int x, y;
+    const int c = classify(rec, i, state + S_T_LAST, H, W, mask, io, e, x, y);
     if (c == C_KEPT && width) {                                  // width 0: rule 3 is off, nothing is looked up
         Entry* en = table_insert(tab, cap, make_key(e.t / width, x, y));
         if (en) { atomicMax(&en->fneg, ~(unsigned)i); atomicMax(&en->m, e.t); }
@@ -93,9 +88,6 @@ __global__ __launch_bounds__(BLOCK) void filter_decide_kernel(const Rec* __restr
                                                               long* __restrict__ state, const Entry* __restrict__ tab,
                                                               unsigned long long cap, unsigned char* __restrict__ cls,
                                                               unsigned long long* __restrict__ tile_off) {
-    __shared__ unsigned lds_c[4];
-    if (threadIdx.x < 4) lds_c[threadIdx.x] = 0;
-    __syncthreads();
     const long i = lo + (long)blockIdx.x * BLOCK + threadIdx.x;
     int c = -1;
     if (i < hi) {
@@ -125,15 +117,7 @@ __global__ __launch_bounds__(BLOCK) void filter_decide_kernel(const Rec* __restr
             if (!ok) { c = C_UNSUPPORTED; cls[i] = (unsigned char)c; }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned n = wave_sum_u32(c == k ? 1u : 0u);
-        if ((threadIdx.x & 63) == 0 && n) atomicAdd(&lds_c[k], n);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) tile_off[i / TILE] = lds_c[C_KEPT];                    // the scan turns the counts into offsets
-    if (threadIdx.x < 4 && lds_c[threadIdx.x])
-        atomicAdd(reinterpret_cast<unsigned long long*>(state + S_KEPT + threadIdx.x), (unsigned long long)lds_c[threadIdx.x]);
+    tally_classes<N_CLASS>(c, tile_off + lo / TILE + blockIdx.x, state + S_KEPT);
 }
 
 // (c) the surface takes every event that passed rules 1 and 2, kept or not
@@ -151,28 +135,7 @@ __global__ __launch_bounds__(BLOCK) void filter_surface_kernel(const Rec* __rest
 // (d) one workgroup: tile counts -> offsets behind the records emitted so far; seen, last time, the times around a decrease
 __global__ __launch_bounds__(BLOCK) void filter_scan_kernel(const Rec* __restrict__ rec, long lo, long hi, long* __restrict__ state,
                                                             unsigned long long* __restrict__ tile_off, long* __restrict__ io) {
-    __shared__ unsigned long long lds_s[BLOCK / 64];
-    unsigned long long base = (unsigned long long)io[IO_EMITTED];
-    const long first = lo / TILE, end = (hi + TILE - 1) / TILE;
-    __syncthreads();                                             // every lane has read io before lane 0 writes it
-    for (long t0 = first; t0 < end; t0 += PASS) {
-        const long tile = t0 + threadIdx.x;
-        const unsigned long long n = tile < end ? tile_off[tile] : 0ULL;
-        unsigned long long sum;
-        const unsigned long long off = base + block_scan_sum(n, sum, lds_s);
-        if (tile < end) tile_off[tile] = off;
-        base += sum;
-    }
-    if (threadIdx.x == 0) {
-        io[IO_EMITTED] = (long)base;
-        const long bad = io[IO_BAD];
-        if (bad >= lo && bad < hi) {
-            io[IO_T_BEFORE] = bad > 0 ? (long)rec[bad - 1].t : state[S_T_LAST];
-            io[IO_T_AT] = (long)rec[bad].t;
-        }
-        state[S_SEEN] += hi - lo;
-        if (hi > lo) state[S_T_LAST] = (long)rec[hi - 1].t;
-    }
+    scan_tiles<S_SEEN, S_T_LAST>(rec, lo, hi, state, tile_off, io);
 }
 
 __global__ __launch_bounds__(BLOCK) void filter_emit_kernel(const Rec* __restrict__ rec, long n_events, const unsigned char* __restrict__ cls,

@@ -33,7 +33,7 @@ constexpr int SCAN_PER_LANE = 16;                                // histogram en
 constexpr int SORT_TILES = 8;                                    // tiles of records per workgroup of the sort: one digit count per 8 x 256 records
 constexpr long WS_TILE = (long)TILE * 16;                        // keys and indices, twice (ping-pong)
 constexpr long WS_HIST = (long)RADIX * 4;                        // the digit counts of one sort tile
-enum { C_OUTSIDE = 1, C_MASKED = 2, C_FLICKER = 3, C_BURST = 4, N_CLASS = 5 };           // C_KEPT = 0: a candidate until the walk decides
+enum { C_FLICKER = 3, C_BURST = 4, N_CLASS = 5 };                // behind C_KEPT (a candidate until the walk decides), C_OUTSIDE, C_MASKED
 enum { S_SEEN = 0, S_KEPT, S_OUTSIDE, S_MASKED, S_FLICKER, S_BURST, S_T_LAST, S_HEAD = 8 };      // state block: include/leod_hip.h
 enum { P_T_PREV = 0, P_T_EDGE, P_PK, P_N_PER, P_LONGS };         // per pixel, behind the head
 enum { KEEP_FIRST = 0, KEEP_SECOND = 1, KEEP_FROM_SECOND = 2 };
@@ -48,13 +48,8 @@ __global__ __launch_bounds__(BLOCK) void pix_classify_kernel(const Rec* __restri
                                                              unsigned* __restrict__ idx, long* __restrict__ io) {
     const long i = lo + (long)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= hi) return;
-    const Rec e = rec[i];
-    const long before = i > 0 ? (long)rec[i - 1].t : state[S_T_LAST];             // -1: nothing seen yet
-    if ((long)e.t < before) atomicMin(reinterpret_cast<long long*>(io + IO_BAD), (long long)i);
-    const int x = (int)(e.xyp & 16383u), y = (int)((e.xyp >> 14) & 16383u);
-    int c = C_KEPT;
-    if (x >= W || y >= H) c = C_OUTSIDE;
-    else if (mask && mask[(long)y * W + x]) c = C_MASKED;
+    Rec e; int x, y;
+    const int c = classify(rec, i, state + S_T_LAST, H, W, mask, io, e, x, y);
     cls[i] = (unsigned char)c;
     key[i - lo] = c == C_KEPT ? (unsigned)y * (unsigned)W + (unsigned)x : 0u;     // H * W <= 2^28
     idx[i - lo] = (unsigned)i;
@@ -188,47 +183,14 @@ __global__ __launch_bounds__(BLOCK) void pix_walk_kernel(const Rec* __restrict__
 // (d) kept records per tile; the five counters
 __global__ __launch_bounds__(BLOCK) void pix_count_kernel(long lo, long hi, const unsigned char* __restrict__ cls, long* __restrict__ state,
                                                           unsigned long long* __restrict__ tile_off) {
-    __shared__ unsigned lds_c[N_CLASS];
-    if (threadIdx.x < N_CLASS) lds_c[threadIdx.x] = 0;
-    __syncthreads();
     const long i = lo + (long)blockIdx.x * BLOCK + threadIdx.x;
-    const int c = i < hi ? (int)cls[i] : -1;
-#pragma unroll
-    for (int k = 0; k < N_CLASS; ++k) {
-        const unsigned m = wave_sum_u32(c == k ? 1u : 0u);
-        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&lds_c[k], m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) tile_off[lo / TILE + blockIdx.x] = lds_c[C_KEPT];      // the scan turns the counts into offsets
-    if (threadIdx.x < N_CLASS && lds_c[threadIdx.x])
-        atomicAdd(reinterpret_cast<unsigned long long*>(state + S_KEPT + threadIdx.x), (unsigned long long)lds_c[threadIdx.x]);
+    tally_classes<N_CLASS>(i < hi ? (int)cls[i] : -1, tile_off + lo / TILE + blockIdx.x, state + S_KEPT);
 }
 
-// (e) as filter_scan_kernel of k_filter.hip, on this state block
+// (e) the scan of the tile counts, on this state block
 __global__ __launch_bounds__(BLOCK) void pix_scan_kernel(const Rec* __restrict__ rec, long lo, long hi, long* __restrict__ state,
                                                          unsigned long long* __restrict__ tile_off, long* __restrict__ io) {
-    __shared__ unsigned long long lds_s[BLOCK / 64];
-    unsigned long long base = (unsigned long long)io[IO_EMITTED];
-    const long first = lo / TILE, end = (hi + TILE - 1) / TILE;
-    __syncthreads();                                             // every lane has read io before lane 0 writes it
-    for (long t0 = first; t0 < end; t0 += PASS) {
-        const long tile = t0 + threadIdx.x;
-        const unsigned long long m = tile < end ? tile_off[tile] : 0ULL;
-        unsigned long long sum;
-        const unsigned long long off = base + block_scan_sum(m, sum, lds_s);
-        if (tile < end) tile_off[tile] = off;
-        base += sum;
-    }
-    if (threadIdx.x == 0) {
-        io[IO_EMITTED] = (long)base;
-        const long bad = io[IO_BAD];
-        if (bad >= lo && bad < hi) {
-            io[IO_T_BEFORE] = bad > 0 ? (long)rec[bad - 1].t : state[S_T_LAST];
-            io[IO_T_AT] = (long)rec[bad].t;
-        }
-        state[S_SEEN] += hi - lo;
-        if (hi > lo) state[S_T_LAST] = (long)rec[hi - 1].t;
-    }
+    scan_tiles<S_SEEN, S_T_LAST>(rec, lo, hi, state, tile_off, io);
 }
 
 int key_bits(int H, int W) {                                     // ceil(log2(H * W)): 0 for one pixel

@@ -13,15 +13,17 @@ Window rule (the project's own), D = ``duration_us``:
 ``--write packed`` writes the frames as a packed store (``.evp``, data/utils/packed.py) instead of the raw ``.npy`` twin: every chunk
 of windows is encoded on the device (``ops.pack_frames``) and only the packed bytes come back.
 
-A ``.raw`` file (EVT2 / EVT3; ``data/utils/raw_events.py``) goes to the device as payload bytes, a chunk at a time; ``ops.decode_evt``
-(csrc/k_evt.hip) turns each chunk into the same 8-byte records, which then take the path above window by window.  ``--unlabelled ok``
-accepts recordings without a box file (trees with zero labels, to be pseudo-labelled).
+An unfiltered ``.dat`` file knows its number of frames in advance (``voxelize_recording``, into an ``open_memmap``).  A ``.raw`` file (EVT2 /
+EVT3; ``data/utils/raw_events.py``), or either container with a filter on, streams through ``voxelize_raw_recording``: the chunk reader
+(``_RecordChunks``: payload bytes through one pinned buffer, ``ops.decode_evt`` of csrc/k_evt.hip with the carried state), the filter chain
+(``_FilterChain``: what reaches the voxeliser, the order check, the filters' part of the report) and one loop body that cuts complete windows
+and carries the rest.  ``_TreeWriter`` writes the tree of both.  ``--unlabelled ok`` accepts recordings without a box file (zero labels).
 
 Noise filters (off by default; the rule: DESIGN.md section 1; ``ops.filter_events``, csrc/k_filter.hip): ``--pixel-mask FILE.npy`` removes
 the events of the masked pixels, ``--hot-rate HZ`` first counts the recording's events per pixel on the device and masks the pixels that
 fire faster (the mask is written beside the frames as ``hot_pixels.npy``), ``--denoise-us N`` keeps an event only if one of its 8
-neighbours fired at most N microseconds before it.  With one of them given, both containers take the streaming route of the ``.raw``
-files, at sensor resolution; the number of frames, the window edges and the label files are those of the unfiltered recording.
+neighbours fired at most N microseconds before it.  With one of them given, both containers take the streaming route, at sensor
+resolution; the number of frames, the window edges and the label files are those of the unfiltered recording.
 
 Per-pixel filters (off by default; the rule: DESIGN.md section 1; ``ops.pixel_filter_events``, csrc/k_pixfilter.hip): ``--trail-us N`` keeps
 the first event of every burst of same-polarity events of a pixel that follow each other within N microseconds, ``--stc-us N`` keeps a
@@ -34,13 +36,14 @@ sequences, and apply the bounds and the mask; ``--denoise-us`` then sees what th
                                    [--trail-us N | --stc-us N [--stc-cut-trail]] [--anti-flicker FMIN:FMAX [--flicker-lock N]]
 """
 import argparse
+import contextlib
 import glob
 import os
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from leod_amd.data.utils import dat_events
+from leod_amd.data.utils import dat_events, event_filter as ef
 from leod_amd.data.utils.types import DatasetType
 
 # labels.npz 'labels': the tree's 40-byte label record (data/genx_utils/labels.py reads it by field name)
@@ -191,39 +194,131 @@ class _NpyStream:
                 os.remove(fn)
 
 
+class _RecordChunks:
+    """The chunk reader: iterating yields the device records (uint8 [n, 8]) of ``raw_chunk_bytes`` of ``payload`` at a time -- the payload
+    of a .raw file, decoded with the carried state (``ops.decode_evt``; a time outside [0, 2^32) us raises ``ValueError``), or with
+    ``encoding`` 'dat' the bytes of .dat records, cut at whole records.  ``counters()``: the decoder's so far (zeros for 'dat').  ONE pinned
+    buffer: it is written again only after the event recorded right behind its non-blocking copy to the device has passed."""
+
+    def __init__(self, payload: np.ndarray, encoding: str, raw_chunk_bytes: int, device, what: str):
+        step = int(raw_chunk_bytes)
+        if step < 4 or step % 4:
+            raise ValueError(f'raw_chunk_bytes={step}: a positive multiple of 4 expected')
+        self.step = max(step // 8, 1) * 8 if encoding == 'dat' else step         # whole records
+        self.payload, self.encoding, self.device, self.what, self.state = payload, encoding, device, what, None
+
+    def __iter__(self):
+        import torch
+        from leod_amd import ops
+        payload, step, copied = self.payload, self.step, None
+        pin = torch.empty((min(step, max(len(payload), 4)),), dtype=torch.uint8).pin_memory()
+        for pos in range(0, len(payload), step):
+            n = min(step, len(payload) - pos)
+            if copied is not None:
+                copied.synchronize()                             # the copy of the chunk before has left the pinned buffer
+            pin.numpy()[:n] = payload[pos:pos + n]               # the host fills it while the device works on the chunk before
+            rec = pin[:n].to(self.device, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record()
+            if self.encoding == 'dat':
+                rec = rec.view(-1, 8)
+            else:
+                rec, self.state = ops.decode_evt(rec, self.encoding, self.state)
+                if int(self.state[12].item()):
+                    raise ValueError(f'{self.what}: an event time lies outside [0, 2^32) microseconds after the shift by the first '
+                                     'TIME_HIGH; it does not fit a .dat record')
+            yield rec
+
+    def counters(self) -> Dict:
+        from leod_amd import ops
+        zeros = dict(events=0, early_events=0, ignored_words=0, unknown_words=0, overflow=0, wraps=0)
+        return zeros if self.state is None else ops.evt_state_counters(self.state)
+
+
+def _order_error(what: str, t_before: int, t_at: int) -> ValueError:
+    return ValueError(f'{what}: timestamps decrease ({t_before} -> {t_at}); a recording must be sorted in time')
+
+
+def _report_fragment(frames: int, dropped: int, decoder: Dict, first: Optional[str] = None, tau_on: bool = False,
+                     activity: Optional[Dict] = None, pixel: Optional[Dict] = None) -> Dict:
+    """What ``voxelize_raw_recording`` returns, from plain numbers: the decoder's counters, the voxeliser's ``dropped``, ``first`` the stage
+    that saw every event and applied the bounds and the mask (None: no filter; 'activity': ``ops.filter_events``; 'pixel': that op, followed
+    by ``ops.filter_events`` iff ``tau_on``), ``activity`` / ``pixel`` the counters of the ops' states (None: no state yet, zeros).
+    ``kept_events`` is what reached the voxeliser, ``events`` the first stage's ``seen``, its ``outside`` joins ``dropped_events``."""
+    rep = dict(frames=frames, dropped_events=dropped, **decoder)
+    if first is None:
+        return rep
+    fc = activity or dict(seen=0, kept=0, outside=0, masked=0, unsupported=0)
+    pc = pixel or dict(seen=0, kept=0, outside=0, masked=0, flicker=0, burst=0)
+    head = pc if first == 'pixel' else fc
+    rep.update(events=head['seen'], dropped_events=dropped + head['outside'], masked_events=head['masked'],
+               unsupported_events=fc['unsupported'], kept_events=pc['kept'] if first == 'pixel' and not tau_on else fc['kept'])
+    if first == 'pixel':
+        rep.update(flicker_events=pc['flicker'], burst_events=pc['burst'])
+    return rep
+
+
+class _FilterChain:
+    """The filter chain of one recording, built once from ``event_filter``: None, or dict(tau_us: int or None, mask: uint8 [H, W] or None,
+    pixel: None or the dict of ``check_pixel_filter_options``).  Calling it on a chunk's records returns those that reach the voxeliser
+    and carries the states.  With ``pixel``: ``ops.pixel_filter_events`` first, which applies the bounds and the mask and needs whole
+    per-pixel sequences; ``ops.filter_events`` follows only where ``tau_us`` is set, only on a non-empty result, and without the mask.
+    Else ``ops.filter_events`` with the mask.  Times that decrease -- against the chunk before, too -- raise one ``ValueError``."""
+
+    def __init__(self, event_filter: Optional[Dict], sensor_hw, device, what: str):
+        import torch
+        self.hw, self.what, self.pstate, self.fstate = tuple(sensor_hw), what, None, None
+        self.tau_us, mask, self.pixel = (event_filter[k] for k in ('tau_us', 'mask', 'pixel')) if event_filter else (None, None, None)
+        self.first = None if event_filter is None else 'activity' if self.pixel is None else 'pixel'
+        self.mask = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)).to(device)
+        self.t_seen = torch.full((1,), -1, dtype=torch.int64, device=device) if event_filter is None else None
+
+    def __call__(self, rec):
+        import torch
+        from leod_amd import ops
+        if self.first is None:                                   # no stage: the order check alone, on the device
+            t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
+            bad = torch.nonzero(torch.cat([t[:1] < self.t_seen, t[1:] < t[:-1]]))
+            if bad.numel():                                      # position 0: earlier than the last event of the chunk before
+                t, i = torch.cat([self.t_seen, t]), int(bad[0])
+                raise _order_error(self.what, int(t[i]), int(t[i + 1]))
+            self.t_seen = t[-1:].clone()
+            return rec
+        try:
+            if self.first == 'pixel':
+                rec, self.pstate = ops.pixel_filter_events(rec, *self.hw, state=self.pstate, pixel_mask=self.mask, **self.pixel)
+                if self.tau_us is not None and rec.shape[0]:
+                    rec, self.fstate = ops.filter_events(rec, *self.hw, self.tau_us, state=self.fstate)
+            else:
+                rec, self.fstate = ops.filter_events(rec, *self.hw, self.tau_us, state=self.fstate, pixel_mask=self.mask)
+        except ops.EventOrderError as e:
+            raise _order_error(self.what, e.t_before, e.t_at) from None
+        return rec
+
+    def report(self, frames: int, dropped: int, decoder: Dict) -> Dict:
+        from leod_amd import ops
+        return _report_fragment(frames, dropped, decoder, self.first, self.tau_us is not None,
+                                ops.event_filter_counters(self.fstate) if self.fstate is not None else None,
+                                ops.pixel_filter_counters(self.pstate) if self.pstate is not None else None)
+
+
 def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: bool, duration_us: int, bins: int, height: int, width: int,
                            ds2: bool, what: str, device=None, raw_chunk_bytes: int = RAW_CHUNK_BYTES,
                            frames_per_copy: int = FRAMES_PER_COPY, event_filter: Optional[Dict] = None) -> Dict:
     """Memory-mapped payload bytes of a .raw file -> frames appended to ``sink`` (``_NpyStream`` or, with ``packed``, a ``PackedWriter``).
-    ``raw_chunk_bytes`` of payload at a time go through one pinned buffer and are decoded with the carried state (``ops.decode_evt``);
-    sortedness and the window offsets of the decoded times are found on the device; every window that is complete -- a later event has
-    been seen -- is voxelised by ``ops.voxelize_dat_windows``, the records of the last, incomplete one are carried into the next chunk.
-    ``event_filter`` (dict(tau_us: int or None, mask: uint8 [H, W] or None)): every chunk's records go through ``ops.filter_events`` with
-    the carried filter state before they join the carry; the filter then checks the order of the times, and the windows are still cut at
-    the times of the events SEEN (one more small read-back per chunk): a window that loses all its events is a zero frame.  With it
-    ``encoding`` may be 'dat': ``payload`` is the bytes of .dat records, which need no decoder.  With ``event_filter['pixel']``
-    (dict(burst_us, burst_keep, flicker) of ``check_pixel_filter_options``) the records first go through ``ops.pixel_filter_events``,
-    which applies the bounds and the mask and needs whole per-pixel sequences; ``ops.filter_events`` follows only where ``tau_us`` is
-    set, and the report also holds flicker_events and burst_events.
-    -> dict(frames, dropped_events and the decoder's counters; with a filter also kept_events, masked_events, unsupported_events)."""
+    ``_RecordChunks`` brings the records of ``raw_chunk_bytes`` of payload at a time; ``_FilterChain`` (from ``event_filter``) checks the
+    order of their times and hands on those that reach the voxeliser; every window that is complete -- a later event has been seen -- is
+    voxelised by ``ops.voxelize_dat_windows``, the records of the last, incomplete one are carried into the next chunk.  A window that
+    loses all its events is a zero frame.  With ``event_filter`` ``encoding`` may be 'dat' (.dat record bytes).  -> ``_report_fragment``."""
     import torch
     from leod_amd import ops
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    raw_chunk_bytes = int(raw_chunk_bytes)
-    if raw_chunk_bytes < 4 or raw_chunk_bytes % 4:
-        raise ValueError(f'raw_chunk_bytes={raw_chunk_bytes}: a positive multiple of 4 expected')
-    if encoding == 'dat':
-        assert event_filter is not None, 'unfiltered .dat records take voxelize_recording'
-        raw_chunk_bytes = max(raw_chunk_bytes // 8, 1) * 8       # whole records
+    chunks = _RecordChunks(payload, encoding, raw_chunk_bytes, device, what)
+    assert encoding != 'dat' or event_filter is not None, 'unfiltered .dat records take voxelize_recording'
+    chain = _FilterChain(event_filter, (height, width), device, what)
     D = int(duration_us)
-    pin = torch.empty((min(raw_chunk_bytes, max(len(payload), 4)),), dtype=torch.uint8).pin_memory()
-    pin_np = pin.numpy()
     dropped = torch.zeros((1,), dtype=torch.int64, device=device)
-    state, carry, done, t_last = None, torch.empty((0, 8), dtype=torch.uint8, device=device), 0, 0
-    fstate, fmask = None, None
-    pixel, pstate = (event_filter or {}).get('pixel'), None
-    if event_filter is not None and event_filter.get('mask') is not None:
-        fmask = torch.from_numpy(np.ascontiguousarray(event_filter['mask'], dtype=np.uint8)).to(device)
+    carry, done, t_last = torch.empty((0, 8), dtype=torch.uint8, device=device), 0, 0
 
     def emit(rec, off):                                          # windows `done` .. of rec, offsets [k + 1] on the device
         nonlocal done, dropped
@@ -241,46 +336,15 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
         done += n_win
 
     with torch.cuda.device(device):
-        for pos in range(0, len(payload), raw_chunk_bytes):
-            n = min(raw_chunk_bytes, len(payload) - pos)
-            pin_np[:n] = payload[pos:pos + n]
-            if encoding == 'dat':
-                rec = pin[:n].to(device, non_blocking=True).view(-1, 8)
-            else:
-                rec, state = ops.decode_evt(pin[:n].to(device, non_blocking=True), encoding, state)
-                if int(state[12].item()):
-                    raise ValueError(f'{what}: an event time lies outside [0, 2^32) microseconds after the shift by the first TIME_HIGH; '
-                                     'it does not fit a .dat record')
-            if event_filter is not None:
-                if rec.shape[0] == 0:
-                    continue
-                # The time of the last event SEEN, kept or not: it sets the number of frames.  This read-back is one more host
-                # synchronisation per chunk besides the op's own (the kept count), and for 'dat' it is also the FENCE behind the
-                # non-blocking copy out of the pinned buffer, which the next chunk overwrites (for .raw, decode_evt's read-back is).
-                t_last = int(rec.view(torch.int32)[-1, 0]) & 0xffffffff
-                try:
-                    if pixel is not None:
-                        rec, pstate = ops.pixel_filter_events(rec, height, width, state=pstate, pixel_mask=fmask, **pixel)
-                        if event_filter.get('tau_us') is not None and rec.shape[0]:          # bounds and mask are applied already
-                            rec, fstate = ops.filter_events(rec, height, width, event_filter['tau_us'], state=fstate)
-                    else:
-                        rec, fstate = ops.filter_events(rec, height, width, event_filter.get('tau_us'), state=fstate, pixel_mask=fmask)
-                except ops.EventOrderError as e:
-                    raise ValueError(f'{what}: timestamps decrease ({e.t_before} -> {e.t_at}); a recording must be sorted in time') from None
-                rec = torch.cat([carry, rec]) if carry.shape[0] else rec
-                t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
-            else:
-                rec = torch.cat([carry, rec]) if carry.shape[0] else rec
-                if rec.shape[0] == 0:
-                    continue
-                t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
-                bad = torch.nonzero(t[1:] < t[:-1])
-                if bad.numel():                                  # the carried records come first: a decrease across two chunks shows here
-                    i = int(bad[0])
-                    raise ValueError(f'{what}: timestamps decrease ({int(t[i])} -> {int(t[i + 1])}); a recording must be sorted in time')
-                t_last = int(t[-1])
+        for rec in chunks:
+            if rec.shape[0] == 0:
+                continue
+            t_last = int(rec.view(torch.int32)[-1, 0]) & 0xffffffff      # of the events SEEN, kept or not: it sets the number of frames
+            rec = chain(rec)
+            rec = torch.cat([carry, rec]) if carry.shape[0] else rec
             k_last = max(-(-t_last // D) - 1, 0)                  # the window of the last event: everything before it is complete
             if k_last > done:
+                t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
                 edges = torch.arange(done + 1, k_last + 1, dtype=torch.int64, device=device) * D
                 off = torch.cat([torch.zeros((1,), dtype=torch.int64, device=device), torch.searchsorted(t, edges, right=True)])
                 emit(rec, off)
@@ -290,49 +354,23 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
         n_frames = dat_events.num_windows(t_last, D)
         assert n_frames == done + 1
         emit(carry, torch.tensor([0, carry.shape[0]], dtype=torch.int64, device=device))
-        counters = ops.evt_state_counters(state) if state is not None else dict(events=0, early_events=0, ignored_words=0,
-                                                                                unknown_words=0, overflow=0, wraps=0)
-        if event_filter is not None:
-            fc = ops.event_filter_counters(fstate) if fstate is not None else dict(seen=0, kept=0, outside=0, masked=0, unsupported=0)
-            if pixel is not None:                                # the first stage saw every event; the second one its output
-                pc = ops.pixel_filter_counters(pstate) if pstate is not None else dict(seen=0, kept=0, outside=0, masked=0, flicker=0,
-                                                                                       burst=0)
-                kept = fc['kept'] if event_filter.get('tau_us') is not None else pc['kept']
-                return dict(frames=n_frames, dropped_events=int(dropped.item()) + pc['outside'], kept_events=kept,
-                            masked_events=pc['masked'], unsupported_events=fc['unsupported'], flicker_events=pc['flicker'],
-                            burst_events=pc['burst'], **dict(counters, events=pc['seen']))
-            # the filter removes and counts the events outside the sensor: none is left for the voxeliser to drop
-            return dict(frames=n_frames, dropped_events=int(dropped.item()) + fc['outside'], kept_events=fc['kept'],
-                        masked_events=fc['masked'], unsupported_events=fc['unsupported'], **dict(counters, events=fc['seen']))
-    return dict(frames=n_frames, dropped_events=int(dropped.item()), **counters)
+        return chain.report(n_frames, int(dropped.item()), chunks.counters())
 
 
 def count_pixel_events(payload: np.ndarray, encoding: str, height: int, width: int, what: str, device=None,
                        raw_chunk_bytes: int = RAW_CHUNK_BYTES) -> Dict:
     """The first pass of ``--hot-rate``: events per pixel of a whole recording, counted on the device (``ops.event_pixel_counts``) from the
-    payload of a .raw file (decoded a chunk at a time, as ``voxelize_raw_recording`` does) or the bytes of .dat records (``encoding``
-    'dat').  -> dict(counts int64 [H, W], outside, events, t_first, t_last): the times of the first and the last event (0 without any)."""
+    chunks of ``_RecordChunks`` (the payload of a .raw file, or the bytes of .dat records with ``encoding`` 'dat').
+    -> dict(counts int64 [H, W], outside, events, t_first, t_last): the times of the first and the last event (0 without any)."""
     import torch
     from leod_amd import ops
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    raw_chunk_bytes = int(raw_chunk_bytes)
-    if raw_chunk_bytes < 4 or raw_chunk_bytes % 4:
-        raise ValueError(f'raw_chunk_bytes={raw_chunk_bytes}: a positive multiple of 4 expected')
-    if encoding == 'dat':
-        raw_chunk_bytes = max(raw_chunk_bytes // 8, 1) * 8
-    pin = torch.empty((min(raw_chunk_bytes, max(len(payload), 4)),), dtype=torch.uint8).pin_memory()
-    pin_np = pin.numpy()
+    chunks = _RecordChunks(payload, encoding, raw_chunk_bytes, device, what)
     counts = torch.zeros((height, width), dtype=torch.int64, device=device)
     outside = torch.zeros((1,), dtype=torch.int64, device=device)
-    state, first, last, events = None, None, None, 0
+    first, last, events = None, None, 0
     with torch.cuda.device(device):
-        for pos in range(0, len(payload), raw_chunk_bytes):
-            n = min(raw_chunk_bytes, len(payload) - pos)
-            pin_np[:n] = payload[pos:pos + n]
-            if encoding == 'dat':
-                rec = pin[:n].to(device, non_blocking=True).view(-1, 8)
-            else:
-                rec, state = ops.decode_evt(pin[:n].to(device, non_blocking=True), encoding, state)
+        for rec in chunks:
             if rec.shape[0] == 0:
                 continue
             events += rec.shape[0]
@@ -341,12 +379,8 @@ def count_pixel_events(payload: np.ndarray, encoding: str, height: int, width: i
             last = rec[-1].clone()
             _, o = ops.event_pixel_counts(rec, height, width, counts)
             outside += o
-            torch.cuda.current_stream().synchronize()           # the pinned buffer is reused by the next chunk
         t_first = int(first.view(torch.int32)[0]) & 0xffffffff if first is not None else 0
         t_last = int(last.view(torch.int32)[0]) & 0xffffffff if last is not None else 0
-        if state is not None and int(state[12].item()):
-            raise ValueError(f'{what}: an event time lies outside [0, 2^32) microseconds after the shift by the first TIME_HIGH; '
-                             'it does not fit a .dat record')
         return dict(counts=counts.cpu().numpy(), outside=int(outside.item()), events=events, t_first=t_first, t_last=t_last)
 
 
@@ -354,7 +388,6 @@ def check_filter_options(dataset_type, denoise_us=None, pixel_mask=None, hot_rat
     """The three filter options of a call, checked on the host before anything is opened -> None when all are off, else
     dict(tau_us, mask, hot_rate_hz): ``pixel_mask`` (a ``.npy`` file name or an array) read and checked against the sensor of the
     dataset."""
-    from leod_amd.data.utils import event_filter as ef
     if denoise_us is None and pixel_mask is None and hot_rate_hz is None:
         return None
     if denoise_us is not None:
@@ -377,7 +410,6 @@ def check_pixel_filter_options(trail_us=None, stc_us=None, stc_cut_trail=False, 
     arguments of ``ops.pixel_filter_events``: dict(burst_us, burst_keep, flicker).  ``trail_us`` keeps the first event of a burst,
     ``stc_us`` a burst from its second event on (``stc_cut_trail``: the second alone); ``anti_flicker``: 'FMIN:FMAX' or (fmin, fmax) in
     Hz, ``flicker_lock`` (None: 3) the in-band periods in a row after which a pixel is removed."""
-    from leod_amd.data.utils import event_filter as ef
     if trail_us is not None and stc_us is not None:
         raise ValueError('trail_us and stc_us: one burst rule at a time (a trail filter keeps the first event of a burst, STC drops it)')
     if stc_cut_trail not in (False, True):
@@ -405,68 +437,85 @@ def check_pixel_filter_options(trail_us=None, stc_us=None, stc_cut_trail=False, 
     return dict(burst_us=burst_us, burst_keep=burst_keep, flicker=flicker)
 
 
-def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt=None,
-                      pix=None) -> Dict:
-    """A recording through ``voxelize_raw_recording``: a ``.raw`` file (``flt`` and ``pix`` None: as it always was), or, with a noise
-    filter on (``flt`` of ``check_filter_options``, ``pix`` of ``check_pixel_filter_options``), a ``.raw`` or a ``.dat`` file."""
-    ds2 = dataset_type == DatasetType.GEN4
+class _TreeWriter:
+    """What every route writes around its frames.  Creating it checks the header's size against the dataset's sensor (the field named as
+    the container spells it) and resolves ``keep_classes``; nothing is written yet.  ``sink`` opens the frame file of the streaming
+    route, ``labels`` converts the boxes, ``finish`` writes the label files (and ``hot_pixels.npy``) and returns the base report."""
+
+    def __init__(self, ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write):
+        self.height, self.width = SENSOR_HW[dataset_type]
+        names = ('height', 'width') if ev_fn.lower().endswith('.raw') else ('Height', 'Width')
+        for name, got, want in zip(names, (hdr.height, hdr.width), (self.height, self.width)):
+            if got is not None and got != want:
+                raise ValueError(f'{ev_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
+        self.keep_classes = DEFAULT_KEEP_CLASSES[dataset_type] if keep_classes is None else keep_classes
+        self.bbox_fn, self.out_dir, self.duration_us = bbox_fn, out_dir, duration_us
+        self.packed, self.ds2 = write == 'packed', dataset_type == DatasetType.GEN4
+        self.ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
+        self.frame_fn = os.path.join(self.ev_dir, 'event_representations' + ('_ds2_nearest' if self.ds2 else '') +
+                                     ('.evp' if self.packed else '.npy'))
+        self.frame_shape = (2 * bins,) + ((self.height // 2, self.width // 2) if self.ds2 else (self.height, self.width))
+
+    def makedirs(self) -> None:
+        os.makedirs(self.ev_dir, exist_ok=True)
+        os.makedirs(os.path.join(self.out_dir, 'labels_v2'), exist_ok=True)
+
+    @contextlib.contextmanager
+    def sink(self):                                              # the frame file of a route that appends: removed if anything raises
+        self.makedirs()
+        if self.packed:
+            from leod_amd.data.utils.packed import PackedWriter
+            sink = PackedWriter(self.frame_fn, *self.frame_shape)     # writes frame_fn + '.tmp', renamed on close
+        else:
+            sink = _NpyStream(self.frame_fn, self.frame_shape)
+        try:
+            yield sink
+        except BaseException:
+            sink.abort()
+            raise
+        sink.close()
+
+    def labels(self, n_frames: int):
+        boxes = np.load(self.bbox_fn) if self.bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
+        return convert_labels(boxes, n_frames, self.duration_us, self.keep_classes)
+
+    def finish(self, labels, n_frames: int, events: int, dropped: int, hot_mask=None) -> Dict:
+        lab, label_idx, repr_idx = labels
+        if hot_mask is not None:
+            np.save(os.path.join(self.ev_dir, ef.MASK_FILE), hot_mask)       # the mask that was applied: --pixel-mask with it repeats the run
+        np.save(os.path.join(self.ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
+        np.savez(os.path.join(self.out_dir, 'labels_v2', 'labels.npz'), labels=lab, objframe_idx_2_label_idx=label_idx)
+        return dict(recording=self.out_dir, frames=n_frames, events=events, dropped_events=dropped, labelled_frames=int(len(repr_idx)),
+                    boxes=int(len(lab)))
+
+
+def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix) -> Dict:
+    """A ``.raw`` file, or with ``flt`` (``check_filter_options``) or ``pix`` (``check_pixel_filter_options``) either container."""
     is_raw = ev_fn.lower().endswith('.raw')
     if is_raw:
         from leod_amd.data.utils import raw_events
         hdr, payload = raw_events.open_words(ev_fn)
-        encoding, sizes = hdr.encoding, (('height', hdr.height), ('width', hdr.width))
+        encoding = hdr.encoding
     else:
         assert flt is not None or pix is not None, 'an unfiltered .dat recording takes voxelize_recording'
         hdr, records = dat_events.open_records(ev_fn)
-        payload = records.view(np.uint8).reshape(-1)
-        encoding, sizes = 'dat', (('Height', hdr.height), ('Width', hdr.width))
-    height, width = SENSOR_HW[dataset_type]
-    for (name, got), want in zip(sizes, (height, width)):
-        if got is not None and got != want:
-            raise ValueError(f'{ev_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
-    if keep_classes is None:
-        keep_classes = DEFAULT_KEEP_CLASSES[dataset_type]
-    event_filter = mask = None
-    if flt is not None:
-        mask = flt['mask']
-        if flt['hot_rate_hz'] is not None:
-            from leod_amd.data.utils import event_filter as ef
-            seen = count_pixel_events(payload, encoding, height, width, ev_fn, raw_chunk_bytes=raw_chunk_bytes)
-            hot = ef.hot_pixel_mask(seen['counts'], max(seen['t_last'] - seen['t_first'], 1), flt['hot_rate_hz'])
-            mask = hot if mask is None else (mask | hot)
-        event_filter = dict(tau_us=flt['tau_us'], mask=mask)
-    if pix is not None:
-        event_filter = dict(event_filter or dict(tau_us=None, mask=None), pixel=pix)
-    ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
-    os.makedirs(ev_dir, exist_ok=True)
-    os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
-    frame_fn = os.path.join(ev_dir, 'event_representations' + ('_ds2_nearest' if ds2 else '') + ('.npy' if write == 'npy' else '.evp'))
-    frame_shape = (2 * bins,) + ((height // 2, width // 2) if ds2 else (height, width))
-    if write == 'packed':
-        from leod_amd.data.utils.packed import PackedWriter
-        sink = PackedWriter(frame_fn, *frame_shape)
-    else:
-        sink = _NpyStream(frame_fn, frame_shape)
-    try:
-        res = voxelize_raw_recording(payload, encoding, sink, write == 'packed', duration_us, bins, height, width, ds2, ev_fn,
-                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter)
-    except BaseException:
-        sink.abort()
-        raise
-    sink.close()
+        payload, encoding = records.view(np.uint8).reshape(-1), 'dat'
+    tree = _TreeWriter(ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write)
+    filtered = flt is not None or pix is not None
+    tau_us, mask, hot = (flt['tau_us'], flt['mask'], None) if flt is not None else (None, None, None)
     if flt is not None and flt['hot_rate_hz'] is not None:
-        from leod_amd.data.utils import event_filter as ef
-        np.save(os.path.join(ev_dir, ef.MASK_FILE), mask)        # the mask that was applied: --pixel-mask with it repeats the run
-    boxes = np.load(bbox_fn) if bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
-    labels, label_idx, repr_idx = convert_labels(boxes, res['frames'], duration_us, keep_classes)
-    np.save(os.path.join(ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
-    np.savez(os.path.join(out_dir, 'labels_v2', 'labels.npz'), labels=labels, objframe_idx_2_label_idx=label_idx)
-    rep = dict(recording=out_dir, frames=res['frames'], events=res['events'], dropped_events=res['dropped_events'],
-               labelled_frames=int(len(repr_idx)), boxes=int(len(labels)))
+        seen = count_pixel_events(payload, encoding, tree.height, tree.width, ev_fn, raw_chunk_bytes=raw_chunk_bytes)
+        hot = ef.hot_pixel_mask(seen['counts'], max(seen['t_last'] - seen['t_first'], 1), flt['hot_rate_hz'])
+        mask = hot = hot if mask is None else (mask | hot)       # hot_pixels.npy is the mask that was applied
+    event_filter = dict(tau_us=tau_us, mask=mask, pixel=pix) if filtered else None
+    with tree.sink() as sink:
+        res = voxelize_raw_recording(payload, encoding, sink, tree.packed, duration_us, bins, tree.height, tree.width, tree.ds2, ev_fn,
+                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter)
+    rep = tree.finish(tree.labels(res['frames']), res['frames'], res['events'], res['dropped_events'], hot_mask=hot)
     if is_raw:
         rep.update(early_events=res['early_events'], ignored_words=res['ignored_words'], unknown_words=res['unknown_words'],
                    clock_wraps=res['wraps'])
-    if flt is not None or pix is not None:
+    if filtered:
         rep.update(kept_events=res['kept_events'], masked_events=res['masked_events'], unsupported_events=res['unsupported_events'],
                    masked_pixels=int(np.count_nonzero(mask)) if mask is not None else 0)
     if pix is not None:
@@ -501,49 +550,26 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
     dataset_type = _dataset_type(dataset_type)
     flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
     pix = check_pixel_filter_options(trail_us, stc_us, stc_cut_trail, anti_flicker, flicker_lock)
-    if pix is not None:
+    if flt is not None or pix is not None or dat_fn.lower().endswith('.raw'):
         return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix)
-    if flt is not None or dat_fn.lower().endswith('.raw'):
-        return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt)
-    ds2 = dataset_type == DatasetType.GEN4
     hdr, records = dat_events.open_records(dat_fn)
-    height, width = SENSOR_HW[dataset_type]
-    for name, got, want in (('Height', hdr.height, height), ('Width', hdr.width, width)):
-        if got is not None and got != want:
-            raise ValueError(f'{dat_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
+    tree = _TreeWriter(dat_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write)
     offsets = dat_events.scan_windows(records, duration_us, what=dat_fn)
     n_frames = len(offsets) - 1
-    if keep_classes is None:
-        keep_classes = DEFAULT_KEEP_CLASSES[dataset_type]
-    boxes = np.load(bbox_fn) if bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
-    labels, label_idx, repr_idx = convert_labels(boxes, n_frames, duration_us, keep_classes)
-
-    ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
-    os.makedirs(ev_dir, exist_ok=True)
-    os.makedirs(os.path.join(out_dir, 'labels_v2'), exist_ok=True)
-    frame_fn = os.path.join(ev_dir, 'event_representations' + ('_ds2_nearest' if ds2 else '') + ('.npy' if write == 'npy' else '.evp'))
-    shape = (n_frames, 2 * bins) + ((height // 2, width // 2) if ds2 else (height, width))
-    if write == 'packed':
-        from leod_amd.data.utils.packed import PackedWriter
-        writer = PackedWriter(frame_fn, *shape[1:])              # writes frame_fn + '.tmp', renamed on close
-        try:
-            dropped = voxelize_recording(records, offsets, None, bins, height, width, ds2, packed_writer=writer)
-        except BaseException:
-            writer.abort()
-            raise
-        writer.close()
+    labels = tree.labels(n_frames)
+    if tree.packed:
+        with tree.sink() as writer:
+            dropped = voxelize_recording(records, offsets, None, bins, tree.height, tree.width, tree.ds2, packed_writer=writer)
     else:
-        mm = np.lib.format.open_memmap(frame_fn + '.tmp', mode='w+', dtype=np.uint8, shape=shape)
+        tree.makedirs()
+        mm = np.lib.format.open_memmap(tree.frame_fn + '.tmp', mode='w+', dtype=np.uint8, shape=(n_frames,) + tree.frame_shape)
         try:
-            dropped = voxelize_recording(records, offsets, mm, bins, height, width, ds2)
+            dropped = voxelize_recording(records, offsets, mm, bins, tree.height, tree.width, tree.ds2)
             mm.flush()
         finally:
             del mm
-        os.replace(frame_fn + '.tmp', frame_fn)
-    np.save(os.path.join(ev_dir, 'objframe_idx_2_repr_idx.npy'), repr_idx)
-    np.savez(os.path.join(out_dir, 'labels_v2', 'labels.npz'), labels=labels, objframe_idx_2_label_idx=label_idx)
-    return dict(recording=out_dir, frames=n_frames, events=int(hdr.n_events), dropped_events=dropped, labelled_frames=int(len(repr_idx)),
-                boxes=int(len(labels)))
+        os.replace(tree.frame_fn + '.tmp', tree.frame_fn)
+    return tree.finish(labels, n_frames, int(hdr.n_events), dropped)
 
 
 def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50_000, bins: int = 10,

@@ -1671,24 +1671,35 @@ def decode_evt(words_u8, fmt, state=None, out=None):
     new = torch.empty_like(state)
     check(_l().leod_evt_scan(_p(words_u8), n_words, fmt, _p(state), _p(new), _p(ws), ws_bytes, _stream()), 'decode_evt (scan)')
     n = int(new[14].item())
-    if out is None:
-        buf = torch.empty((n, 8), dtype=torch.uint8, device=dev)
-    else:
-        _ck(out, torch.uint8, 'out')
-        if out.numel() < n * 8:
-            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {n} records of the chunk')
-        if out.data_ptr() % 8:
-            raise LeodHipError('out: an 8-byte aligned buffer expected')
-        buf = out.reshape(-1)[:n * 8].view(n, 8)
+    buf = _records_out(out, n, dev, 'records of the chunk')
     check(_l().leod_evt_emit(_p(words_u8), n_words, fmt, _p(ws), ws_bytes, _p(buf), n, _p(new), _stream()), 'decode_evt (emit)')
     return buf, new
 
 
+def _records_out(out, n, dev, what):
+    """Where an op stores its ``n`` records: a fresh [n, 8], or the first n * 8 bytes of the caller's ``out`` as the view [n, 8]."""
+    if out is None:
+        return torch.empty((n, 8), dtype=torch.uint8, device=dev)
+    _ck(out, torch.uint8, 'out')
+    if out.numel() < n * 8:
+        raise LeodHipError(f'out: {out.numel()} bytes do not hold the {n} {what}')
+    if out.data_ptr() % 8:
+        raise LeodHipError('out: an 8-byte aligned buffer expected')
+    return out.reshape(-1)[:n * 8].view(n, 8)
+
+
+def _state_counters(state, table, head=None, noun=None):
+    """The counters ``table`` (name -> index) of a state block, one read-back of its first ``head`` words (None: all of it)."""
+    _ck(state, torch.int64, 'state')
+    if head is not None and state.numel() < head:
+        raise LeodHipError(f'state: {noun} state expected, got {tuple(state.shape)}')
+    host = state[:head].cpu().tolist()
+    return {k: int(host[i]) for k, i in table.items()}
+
+
 def evt_state_counters(state):
     """The counters of a decoder state (one read-back): events, early_events, ignored_words, unknown_words, overflow, wraps."""
-    _ck(state, torch.int64, 'state')
-    host = state.cpu().tolist()
-    return {k: int(host[i]) for k, i in _EVT_COUNTERS.items()}
+    return _state_counters(state, _EVT_COUNTERS)
 
 
 # scratch of one piece of a chunk of ``filter_events`` (the (slot, pixel) table of csrc/k_filter.hip): 64 MiB takes 2^21 records in one
@@ -1725,13 +1736,49 @@ def _ck_records(records_u8):
         raise LeodHipError(f'records: {records_u8.numel()} bytes are no whole number of 8-byte events')
     if records_u8.data_ptr() % 8:
         records_u8 = records_u8.clone()                          # the kernels load a record at a time; a fresh allocation is aligned
-    return records_u8, records_u8.numel() // 8
+    n = records_u8.numel() // 8
+    if n >= 1 << 31:
+        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
+    return records_u8, n
 
 
 def _ck_sensor(height, width):
     for name, v in (('height', height), ('width', width)):
         if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384:
             raise LeodHipError(f'{name}={v!r}: an integer in [1, 16384] expected')
+
+
+def _ck_pixel_mask(pixel_mask, height, width):
+    if pixel_mask is None:
+        return
+    if not isinstance(pixel_mask, torch.Tensor) or pixel_mask.dtype not in (torch.uint8, torch.bool):
+        raise LeodHipError(f'pixel_mask: a uint8 or bool tensor expected, got {getattr(pixel_mask, "dtype", type(pixel_mask))}')
+    _ck(pixel_mask, pixel_mask.dtype, 'pixel_mask')
+    if tuple(pixel_mask.shape) != (height, width):
+        raise LeodHipError(f'pixel_mask: shape {tuple(pixel_mask.shape)}, the sensor is {(height, width)}')
+
+
+def _filter_state(state, n_state, height, width):
+    """A checked copy of the state block a filter call was given (None: the caller starts a recording with its initial block)."""
+    if state is None:
+        return None
+    _ck(state, torch.int64, 'state')
+    if state.numel() != n_state:
+        raise LeodHipError(f'state: {n_state} int64 expected for a {height} x {width} sensor, got {tuple(state.shape)}')
+    return state.clone()
+
+
+def _scan_and_emit(name, scan, records_u8, n, marks, marks_bytes, out):
+    """What both filters do around their scan entry point: the io block (csrc/filter_common.hpp: records emitted, first bad position,
+    the two times around it), ``scan(io)``, ONE read-back -- the kept count, or ``EventOrderError`` -- and the emit of the kept records."""
+    io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(records_u8.device)
+    check(scan(_p(io)), f'{name} (scan)')
+    m, bad, t_before, t_at = io.cpu().tolist()
+    if bad != _LONG_MAX:
+        raise EventOrderError(bad, t_before, t_at)
+    buf = _records_out(out, m, records_u8.device, 'records the filter keeps')
+    check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), f'{name} (emit)')
+    return buf
 
 
 def filter_events(records_u8, height, width, tau_us, state=None, pixel_mask=None, out=None, ws_bytes=None):
@@ -1750,23 +1797,12 @@ def filter_events(records_u8, height, width, tau_us, state=None, pixel_mask=None
         raise LeodHipError(f'tau_us={tau_us!r}: an integer in [0, 2^31) expected (None: bounds and mask only)')
     records_u8, n = _ck_records(records_u8)
     dev = records_u8.device
-    if n >= 1 << 31:
-        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
-    if pixel_mask is not None:
-        if not isinstance(pixel_mask, torch.Tensor) or pixel_mask.dtype not in (torch.uint8, torch.bool):
-            raise LeodHipError(f'pixel_mask: a uint8 or bool tensor expected, got {getattr(pixel_mask, "dtype", type(pixel_mask))}')
-        _ck(pixel_mask, pixel_mask.dtype, 'pixel_mask')
-        if tuple(pixel_mask.shape) != (height, width):
-            raise LeodHipError(f'pixel_mask: shape {tuple(pixel_mask.shape)}, the sensor is {(height, width)}')
+    _ck_pixel_mask(pixel_mask, height, width)
     n_state = FILTER_STATE_HEAD + height * width
-    if state is None:
+    new = _filter_state(state, n_state, height, width)
+    if new is None:
         new = torch.full((n_state,), -1, dtype=torch.int64, device=dev)
         new[:FILTER_STATE_HEAD] = torch.tensor([0, 0, 0, 0, 0, -1, 0, 0], dtype=torch.int64)
-    else:
-        _ck(state, torch.int64, 'state')
-        if state.numel() != n_state:
-            raise LeodHipError(f'state: {n_state} int64 expected for a {height} x {width} sensor, got {tuple(state.shape)}')
-        new = state.clone()
     ws_bytes = FILTER_WS_BYTES if ws_bytes is None else int(ws_bytes)
     if ws_bytes < FILTER_WS_MIN_BYTES:
         raise LeodHipError(f'ws_bytes={ws_bytes}: at least {FILTER_WS_MIN_BYTES} expected')
@@ -1774,32 +1810,14 @@ def filter_events(records_u8, height, width, tau_us, state=None, pixel_mask=None
     table_bytes = min(table_bytes, ws_bytes)
     table = torch.empty((max(table_bytes, 16) // 8,), dtype=torch.int64, device=dev)
     marks = torch.empty((max(marks_bytes, 8) // 8,), dtype=torch.int64, device=dev)
-    io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(dev)
-    check(_l().leod_event_filter_scan(_p(records_u8), n, height, width, -1 if tau_us is None else tau_us, _p(pixel_mask), _p(new), _p(table), table_bytes,
-                                       _p(marks), marks_bytes, _p(io), _stream()), 'filter_events (scan)')
-    m, bad, t_before, t_at = io.cpu().tolist()
-    if bad != _LONG_MAX:
-        raise EventOrderError(bad, t_before, t_at)
-    if out is None:
-        buf = torch.empty((m, 8), dtype=torch.uint8, device=dev)
-    else:
-        _ck(out, torch.uint8, 'out')
-        if out.numel() < m * 8:
-            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {m} records the filter keeps')
-        if out.data_ptr() % 8:
-            raise LeodHipError('out: an 8-byte aligned buffer expected')
-        buf = out.reshape(-1)[:m * 8].view(m, 8)
-    check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), 'filter_events (emit)')
-    return buf, new
+    scan = lambda io: _l().leod_event_filter_scan(_p(records_u8), n, height, width, -1 if tau_us is None else tau_us, _p(pixel_mask),      # noqa: E731
+                                                  _p(new), _p(table), table_bytes, _p(marks), marks_bytes, io, _stream())
+    return _scan_and_emit('filter_events', scan, records_u8, n, marks, marks_bytes, out), new
 
 
 def event_filter_counters(state):
     """The counters of a filter state (one read-back): seen, kept, outside, masked, unsupported."""
-    _ck(state, torch.int64, 'state')
-    if state.numel() < FILTER_STATE_HEAD:
-        raise LeodHipError(f'state: a filter state expected, got {tuple(state.shape)}')
-    host = state[:FILTER_STATE_HEAD].cpu().tolist()
-    return {k: int(host[i]) for k, i in _FILTER_COUNTERS.items()}
+    return _state_counters(state, _FILTER_COUNTERS, FILTER_STATE_HEAD, 'a filter')
 
 
 # scratch of one piece of a chunk of ``pixel_filter_events`` (keys and indices of the sort of csrc/k_pixfilter.hip, twice, and its digit
@@ -1862,23 +1880,11 @@ def pixel_filter_events(records_u8, height, width, burst_us=None, burst_keep='fi
     p_min, p_max, lock = _ck_flicker(flicker)
     records_u8, n = _ck_records(records_u8)
     dev = records_u8.device
-    if n >= 1 << 31:
-        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
-    if pixel_mask is not None:
-        if not isinstance(pixel_mask, torch.Tensor) or pixel_mask.dtype not in (torch.uint8, torch.bool):
-            raise LeodHipError(f'pixel_mask: a uint8 or bool tensor expected, got {getattr(pixel_mask, "dtype", type(pixel_mask))}')
-        _ck(pixel_mask, pixel_mask.dtype, 'pixel_mask')
-        if tuple(pixel_mask.shape) != (height, width):
-            raise LeodHipError(f'pixel_mask: shape {tuple(pixel_mask.shape)}, the sensor is {(height, width)}')
-    n_state = PIXFILTER_STATE_HEAD + PIXFILTER_PIXEL_LONGS * height * width
-    if state is None:
+    _ck_pixel_mask(pixel_mask, height, width)
+    new = _filter_state(state, PIXFILTER_STATE_HEAD + PIXFILTER_PIXEL_LONGS * height * width, height, width)
+    if new is None:
         new = torch.tensor([-1, -1, 0, 0], dtype=torch.int64, device=dev).repeat(height * width + 2)
         new[:PIXFILTER_STATE_HEAD] = torch.tensor([0, 0, 0, 0, 0, 0, -1, 0], dtype=torch.int64)
-    else:
-        _ck(state, torch.int64, 'state')
-        if state.numel() != n_state:
-            raise LeodHipError(f'state: {n_state} int64 expected for a {height} x {width} sensor, got {tuple(state.shape)}')
-        new = state.clone()
     _, _, _, need, marks_bytes = pixel_filter_query(n, height, width)
     least = pixel_filter_query(1, height, width)[3]
     ws_bytes = PIXFILTER_WS_BYTES if ws_bytes is None else int(ws_bytes)
@@ -1887,33 +1893,15 @@ def pixel_filter_events(records_u8, height, width, burst_us=None, burst_keep='fi
     ws_bytes = min(need, ws_bytes)
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
     marks = torch.empty((max(marks_bytes, 8) // 8,), dtype=torch.int64, device=dev)
-    io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(dev)
-    check(_l().leod_pixel_filter_scan(_p(records_u8), n, height, width, -1 if burst_us is None else burst_us, PIXFILTER_KEEP[burst_keep],
-                                       p_min, p_max, lock, _p(pixel_mask), _p(new), _p(ws), ws_bytes, _p(marks), marks_bytes, _p(io),
-                                       _stream()), 'pixel_filter_events (scan)')
-    m, bad, t_before, t_at = io.cpu().tolist()
-    if bad != _LONG_MAX:
-        raise EventOrderError(bad, t_before, t_at)
-    if out is None:
-        buf = torch.empty((m, 8), dtype=torch.uint8, device=dev)
-    else:
-        _ck(out, torch.uint8, 'out')
-        if out.numel() < m * 8:
-            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {m} records the filter keeps')
-        if out.data_ptr() % 8:
-            raise LeodHipError('out: an 8-byte aligned buffer expected')
-        buf = out.reshape(-1)[:m * 8].view(m, 8)
-    check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), 'pixel_filter_events (emit)')
-    return buf, new
+    scan = lambda io: _l().leod_pixel_filter_scan(_p(records_u8), n, height, width, -1 if burst_us is None else burst_us,                  # noqa: E731
+                                                  PIXFILTER_KEEP[burst_keep], p_min, p_max, lock, _p(pixel_mask), _p(new), _p(ws), ws_bytes,
+                                                  _p(marks), marks_bytes, io, _stream())
+    return _scan_and_emit('pixel_filter_events', scan, records_u8, n, marks, marks_bytes, out), new
 
 
 def pixel_filter_counters(state):
     """The counters of a per-pixel filter state (one read-back): seen, kept, outside, masked, flicker, burst."""
-    _ck(state, torch.int64, 'state')
-    if state.numel() < PIXFILTER_STATE_HEAD:
-        raise LeodHipError(f'state: a per-pixel filter state expected, got {tuple(state.shape)}')
-    host = state[:PIXFILTER_STATE_HEAD].cpu().tolist()
-    return {k: int(host[i]) for k, i in _PIXFILTER_COUNTERS.items()}
+    return _state_counters(state, _PIXFILTER_COUNTERS, PIXFILTER_STATE_HEAD, 'a per-pixel filter')
 
 
 def event_pixel_counts(records_u8, height, width, counts=None):
@@ -1923,8 +1911,6 @@ def event_pixel_counts(records_u8, height, width, counts=None):
     _ck_sensor(height, width)
     records_u8, n = _ck_records(records_u8)
     dev = records_u8.device
-    if n >= 1 << 31:
-        raise LeodHipError(f'records: {n} events in one chunk; at most 2^31 - 1')
     if counts is None:
         counts = torch.zeros((height, width), dtype=torch.int64, device=dev)
     _ck(counts, torch.int64, 'counts')
