@@ -9,6 +9,7 @@ into ``param.grad`` (allocated once, or a view into the flat gradient buffer set
 inputs; parameters are still passed to ``apply`` so that the outputs are attached to the graph.
 """
 import os
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -559,185 +560,187 @@ class ConvLSTMSeqFn(Function):
 
 
 # ---------------------------------------------------------------------------------------------------
-class BaseConvFn(Function):
-    """BaseConv (network_blocks.py:29-51): conv(no bias) -> BatchNorm2d -> SiLU on NHWC maps."""
-
-    @staticmethod
-    def forward(ctx, mod, x, conv_w, bn_w, bn_b, stride: int, training: bool):
-        if not training:
-            return ops.conv_nhwc_fwd(x, conv_w, None, stride=stride,
-                                     bn=(bn_w, bn_b, mod.bn.running_mean, mod.bn.running_var), bn_eps=mod.bn.eps)
-        need = any(ctx.needs_input_grad)
-        y, saved = _conv_bn_fwd([(mod, x, conv_w, bn_w, bn_b, stride)], need)[0]
-        if need:
-            ctx.mod, ctx.stride = mod, stride
-            ctx.count, ctx.count_dev = saved[-2], saved[-1]
-            ctx.save_for_backward(x, *saved[:-2], conv_w, bn_w, bn_b)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, z, mean, rstd, conv_w, bn_w, bn_b = ctx.saved_tensors
-        dx = _conv_bn_bwd([(ctx.mod, x, z, mean, rstd, conv_w, bn_w, bn_b, ctx.stride, ctx.count, ctx.count_dev, _rows(dy),
-                            ctx.needs_input_grad[1])])[0]
-        return None, dx, None, None, None, None, None
+@dataclass
+class ConvBN:
+    """One member of a conv(no bias) -> BatchNorm2d -> SiLU group on NHWC maps (BaseConv, network_blocks.py:29-51): what the forward
+    pass is given, what it leaves for the backward pass, and what the backward pass is given."""
+    mod: torch.nn.Module
+    x: torch.Tensor
+    conv_w: torch.Tensor
+    bn_w: torch.Tensor
+    bn_b: torch.Tensor
+    stride: int
+    z: Optional[torch.Tensor] = None            # conv output; mean / rstd: the batch statistics BN + SiLU applied to it
+    mean: Optional[torch.Tensor] = None
+    rstd: Optional[torch.Tensor] = None
+    count: int = 0                              # rows behind the statistics; SyncBatchNorm: rows per image, times count_dev on the device
+    count_dev: Optional[torch.Tensor] = None
+    dy: Optional[torch.Tensor] = None           # backward: gradient of the output (zeros from autograd where none arrived); does x want one?
+    need_dx: bool = False
+    stats: Optional[torch.Tensor] = None        # the member's [R, 2, N] slice of the statistics block of the pass at hand
 
 
-def _conv_bn_fwd(members, need):
+def _stat_block(maps, channels, replicas, device, sync):
+    """The zero-filled statistics block of one pass over a group -- contiguous, so that ONE all-reduce carries it -- and every member's
+    [R, 2, N] slice of it: the producers spread their closing atomics over R copies, the consumers fold them.  maps: (images, pixels per
+    image) of each member's conv output; replicas: rows -> R (``ops.stat_replicas`` forward, ``ops.bn_bwd_replicas`` backward).
+    SyncBatchNorm: 32 images stand in for this rank's own count, which depends on the data, while the layout of an all-reduced block
+    must be the same on every rank."""
+    reps = [replicas((32 if sync else images) * pixels) for images, pixels in maps]
+    sizes = [R * 2 * N for R, N in zip(reps, channels)]
+    block = ops.StatArena.zeros((sum(sizes),), device)
+    return block, [part.view(R, 2, N) for part, R, N in zip(block.split(sizes), reps, channels)]
+
+
+def _dgrad_rounds(keys, need_dx):
+    """Input gradients of a group as rounds of launches.  Members with equal ``keys`` -- (data_ptr, shape, stride) of their input -- read
+    the SAME map (conv1 / conv2 of a CSP layer, the first cls / reg tower convs of a head level) and sum their input gradients in ONE
+    buffer, in the dgrad epilogue, instead of as autograd edges summed by extra add kernels.  The j-th reader of a map goes to round j:
+    no round holds two problems with one output, and a buffer's writer (round 0, accumulate=False) comes before its adders (round j > 0,
+    accumulate=True).  -> ([(buffer, round) | None where need_dx is false] per member, [member indices, in member order] per round)"""
+    plan, readers, rounds = [], {}, []
+    for i, (key, need) in enumerate(zip(keys, need_dx)):
+        if not need:
+            plan.append(None)
+            continue
+        buf, rnd = readers.get(key, (len(readers), 0))
+        readers[key] = (buf, rnd + 1)
+        plan.append((buf, rnd))
+        if rnd == len(rounds):
+            rounds.append([])
+        rounds[rnd].append(i)
+    return plan, rounds
+
+
+def _bn_batches(members, fwd):
+    """The BN + SiLU launches of a group, all or nothing: ONE launch per kernel kind when 1 < n <= 8 members share a channel count (and,
+    forward, eps), else one per member"""
+    kinds = {(m.conv_w.shape[0], m.mod.bn.eps if fwd else None) for m in members}
+    return [members] if 1 < len(members) <= 8 and len(kinds) == 1 else [[m] for m in members]
+
+
+def _group3x3(members, maps, weights) -> bool:      # one channel geometry (the tower convs of a depth over the head levels): ONE launch?
+    return all(m.stride == 1 for m in members) and ops.conv3x3_group_ok(maps, weights)
+
+
+def _conv_bn_fwd(members):
     """Training forward of one or several INDEPENDENT BaseConv layers: all convs (their epilogues accumulate the column
     statistics into one contiguous block), ONE SyncBatchNorm all-reduce for the whole block, then the BN + SiLU kernels.
-    members: (mod, x, conv_w, bn_w, bn_b, stride) -> [(y, (z, mean, rstd, count, count_dev))]."""
-    dev = members[0][1].device
+    Fills z, mean, rstd, count and count_dev of the members -> [y]."""
     sync = _sync_bn_on()
-    # the conv epilogues spread their (sum, sumsq) atomics over R copies (R by output rows), bn_silu_fwd folds them
-    def rows_of(x, stride):
-        # SyncBatchNorm: the block is all-reduced, so its layout must not depend on this rank's (data-dependent) image count
-        return (32 if sync else x.shape[0]) * ((x.shape[1] - 1) // stride + 1) * ((x.shape[2] - 1) // stride + 1)
-    reps = [ops.stat_replicas(rows_of(m[1], m[5])) for m in members]
-    block = ops.StatArena.zeros((sum(2 * R * m[2].shape[0] for m, R in zip(members, reps)),), dev)
-    zs, off, stat_slices = None, 0, []
-    for (mod, x, conv_w, bn_w, bn_b, stride), R in zip(members, reps):
-        N = conv_w.shape[0]
-        stat_slices.append(block[off:off + 2 * R * N].view(R, 2, N))
-        off += 2 * R * N
-    # members of one channel geometry (the tower convs of equal depth over the head levels) as ONE launch
-    if all(m[5] == 1 for m in members) and ops.conv3x3_group_ok([m[1] for m in members], [m[2] for m in members]):
-        zs = ops.conv3x3_group_fwd([m[1] for m in members], [m[2] for m in members], stat_slices)
+    xs, ws = [m.x for m in members], [m.conv_w for m in members]
+    block, stats = _stat_block([(m.x.shape[0], ((m.x.shape[1] - 1) // m.stride + 1) * ((m.x.shape[2] - 1) // m.stride + 1)) for m in members],
+                               [w.shape[0] for w in ws], ops.stat_replicas, xs[0].device, sync)
+    zs = ops.conv3x3_group_fwd(xs, ws, stats) if _group3x3(members, xs, ws) else None
     if zs is None:
-        zs = [ops.conv_nhwc_fwd(x, conv_w, None, stride=stride, colstats=sl) for (mod, x, conv_w, bn_w, bn_b, stride), sl in zip(members, stat_slices)]
+        zs = [ops.conv_nhwc_fwd(m.x, m.conv_w, None, stride=m.stride, colstats=s) for m, s in zip(members, stats)]
     images = _SYNC_BN['images'] if sync else None
     if sync:
         assert images is not None, 'SyncBatchNorm: functions.sync_bn_begin(n_images) must open the pass (YoloXDetector.forward_detect does)'
         _allreduce_stats(block)
-    out = []
-    counts, moms = [], []
-    for (mod, x, conv_w, bn_w, bn_b, stride), z in zip(members, zs):
-        rows = z.numel() // conv_w.shape[0]
-        counts.append(rows // z.shape[0] if sync else rows)        # SyncBN: rows per image; the kernels multiply by ``images``
-        moms.append(mod.bn.momentum if mod.bn.momentum is not None else 0.1)
-        mod.bn_calls_pending = getattr(mod, 'bn_calls_pending', 0) + 1     # flushed into num_batches_tracked lazily (flush_bn_counters)
-    same = len(members) > 1 and len(members) <= 8 and len({(m[2].shape[0], m[0].bn.eps) for m in members}) == 1
-    if same:                                                        # one launch for the layers of one channel count
-        res = ops.bn_silu_fwd_group(zs, stat_slices, [m[3] for m in members], [m[4] for m in members], [m[0].bn.running_mean for m in members],
-                                    [m[0].bn.running_var for m in members], counts, members[0][0].bn.eps, moms,
-                                    count_devs=[images] * len(members))
-    else:
-        res = [ops.bn_silu_fwd(z, sl, m[3], m[4], m[0].bn.running_mean, m[0].bn.running_var, c, eps=m[0].bn.eps, momentum=mo, count_dev=images)
-               for m, z, sl, c, mo in zip(members, zs, stat_slices, counts, moms)]
-    for (y, mean, rstd), z, c in zip(res, zs, counts):
-        out.append((y, (z, mean, rstd, c, images) if need else None))
-    return out
+    for m, z, s in zip(members, zs, stats):
+        rows = z.numel() // z.shape[-1]
+        m.z, m.stats, m.count_dev = z, s, images
+        m.count = rows // z.shape[0] if sync else rows                      # SyncBN: rows per image; the kernels multiply by ``images``
+        m.mod.bn_calls_pending = getattr(m.mod, 'bn_calls_pending', 0) + 1  # flushed into num_batches_tracked lazily (flush_bn_counters)
+    ys = []
+    for batch in _bn_batches(members, fwd=True):
+        bns = [m.mod.bn for m in batch]
+        res = ops.bn_silu_fwd_group([m.z for m in batch], [m.stats for m in batch], [m.bn_w for m in batch], [m.bn_b for m in batch],
+                                    [bn.running_mean for bn in bns], [bn.running_var for bn in bns], [m.count for m in batch], bns[0].eps,
+                                    [bn.momentum if bn.momentum is not None else 0.1 for bn in bns], count_devs=[m.count_dev for m in batch])
+        for m, (y, mean, rstd) in zip(batch, res):
+            m.mean, m.rstd = mean, rstd
+            ys.append(y)
+    return ys
 
 
 def _conv_bn_bwd(members):
-    """Backward of the same group: the (sum du, sum du*xhat) reductions of all members into one block, ONE all-reduce, then
-    per member the BN backward, the weight gradient (side stream) and the input gradient.
-    members: (mod, x, z, mean, rstd, conv_w, bn_w, bn_b, stride, count, count_dev, dy, need_dx) -> [dx | None]."""
-    live = [m for m in members if m[11] is not None]
-    dxs = {}
-    if live:
-        dev = live[0][1].device
-        # the reductions spread their closing atomics over R copies of a member's sums (R by rows), the apply kernels fold them
-        sync = _sync_bn_on()
-
-        def rows_of(z):       # SyncBatchNorm: the block is all-reduced, so its layout must not depend on this rank's image count
-            return (32 if sync else z.shape[0]) * (z.numel() // (z.shape[0] * z.shape[-1]))
-        reps = [ops.bn_bwd_replicas(rows_of(m[2])) for m in live]
-        block = ops.StatArena.zeros((sum(2 * R * m[5].shape[0] for m, R in zip(live, reps)),), dev)
-        off = 0
-        slices = []
-        for (mod, x, z, mean, rstd, conv_w, bn_w, bn_b, stride, count, count_dev, dy, need_dx), R in zip(live, reps):
-            N = conv_w.shape[0]
-            slices.append(block[off:off + 2 * R * N].view(R, 2, N))
-            off += 2 * R * N
-        same = 1 < len(live) <= 8 and len({m[5].shape[0] for m in live}) == 1       # one launch per kernel kind for layers of one channel count
-        if same:
-            ops.bn_silu_bwd_reduce_group([m[11] for m in live], [m[2] for m in live], [m[3] for m in live], [m[4] for m in live],
-                                         [m[6] for m in live], [m[7] for m in live], slices)
-        else:
-            for (mod, x, z, mean, rstd, conv_w, bn_w, bn_b, stride, count, count_dev, dy, need_dx), sl in zip(live, slices):
-                ops.bn_silu_bwd_reduce(dy, z, mean, rstd, bn_w, bn_b, out=sl)
-        _allreduce_stats(block)
-        # SyncBatchNorm while the step is being recorded into launch plans: every exchange closes a plan segment, and a segment can only
-        # end with the side stream joined -- the small weight gradients of the neck / head then stay on the launch stream instead of
-        # forking and joining once per layer (17.97 -> see profiles/r04_*_rccl_force_collectives.txt)
-        from .modules.step_plan import PlanRecorder
-        hold = sync and PlanRecorder.current is not None and not _capture_collectives(_SYNC_BN['group'])
-        prev_hold, WgradSide.hold_main = WgradSide.hold_main, hold or WgradSide.hold_main
-        shared_dx = {}
-        rounds = ([], [])                                   # dgrad problems: (dz, conv_w, x.shape, stride, out, accumulate) -- first writers, then adders
-        if same:
-            dzs = ops.bn_silu_bwd_apply_group([m[11] for m in live], [m[2] for m in live], [m[3] for m in live], [m[4] for m in live],
-                                              [m[6] for m in live], [m[7] for m in live], slices, [grad_buf(m[0].bn.weight) for m in live],
-                                              [grad_buf(m[0].bn.bias) for m in live], [m[9] for m in live], count_devs=[m[10] for m in live])
-        else:
-            dzs = [ops.bn_silu_bwd_apply(dy, z, mean, rstd, bn_w, bn_b, sl, grad_buf(mod.bn.weight), grad_buf(mod.bn.bias), count, count_dev=count_dev)
-                   for (mod, x, z, mean, rstd, conv_w, bn_w, bn_b, stride, count, count_dev, dy, need_dx), sl in zip(live, slices)]
-        wg_done = False
-        if all(m[8] == 1 for m in live) and ops.conv3x3_group_ok([m[1] for m in live], [m[5] for m in live]):
-            with _wgrad_side(*dzs, *[m[1] for m in live]):         # the weight gradients of the group: one launch on the side lane
-                wg_done = ops.conv3x3_group_wgrad(dzs, [m[1] for m in live], [grad_buf(m[0].conv.weight) for m in live])
-        for (mod, x, z, mean, rstd, conv_w, bn_w, bn_b, stride, count, count_dev, dy, need_dx), dz in zip(live, dzs):
-            if not wg_done:
-                with _wgrad_side(dz, x):
-                    ops.conv_nhwc_wgrad(dz, x, grad_buf(mod.conv.weight), None, stride=stride)
-            if not need_dx:
-                dxs[id(mod)] = None
-                continue
-            # members that read the SAME input (conv1 / conv2 of a CSP layer, the first cls / reg tower convs of a head level) add their input
-            # gradients in the dgrad epilogue of the later member instead of as two autograd edges summed by an extra add kernel
-            key = (x.data_ptr(), tuple(x.shape), stride)
-            if key in shared_dx:
-                rounds[1].append((dz, conv_w, x.shape, stride, shared_dx[key], True))
-                dxs[id(mod)] = None
-            else:
-                dxs[id(mod)] = shared_dx[key] = ops._empty(tuple(x.shape), dz)
-                rounds[0].append((dz, conv_w, x.shape, stride, shared_dx[key], False))
-        for probs in rounds:
-            # the input gradients of one round write different buffers: one launch where the members share a channel geometry (head towers)
-            done = False
-            if len(probs) > 1 and all(p[3] == 1 for p in probs) and ops.conv3x3_group_ok([p[0] for p in probs], [p[1].transpose(0, 1) for p in probs]):
-                done = ops.conv3x3_group_dgrad([p[0] for p in probs], [p[1] for p in probs], [p[2] for p in probs], [p[4] for p in probs],
-                                               [p[5] for p in probs])
-            if not done:
-                for dz, conv_w, xshape, stride, out, acc in probs:
-                    ops.conv_nhwc_dgrad(dz, conv_w, xshape, stride=stride, out=out, accumulate=acc)
-        WgradSide.hold_main = prev_hold
-    return [dxs.get(id(m[0])) for m in members]
+    """Backward of the same group: the (sum du, sum du*xhat) reductions of all members into one block, ONE all-reduce, then the BN
+    backward, the weight gradients (side stream) and the input gradients (``_dgrad_rounds``) -> [dx | None] per member."""
+    dxs = [None] * len(members)
+    xs, ws = [m.x for m in members], [m.conv_w for m in members]
+    sync = _sync_bn_on()
+    block, stats = _stat_block([(m.z.shape[0], m.z.numel() // (m.z.shape[0] * m.z.shape[-1])) for m in members], [w.shape[0] for w in ws],
+                               ops.bn_bwd_replicas, xs[0].device, sync)
+    for m, s in zip(members, stats):
+        m.stats = s
+    batches = _bn_batches(members, fwd=False)
+    operands = [list(zip(*[(m.dy, m.z, m.mean, m.rstd, m.bn_w, m.bn_b, m.stats) for m in batch])) for batch in batches]
+    for args in operands:
+        ops.bn_silu_bwd_reduce_group(*args)
+    _allreduce_stats(block)
+    # SyncBatchNorm while the step is being recorded into launch plans: every exchange closes a plan segment, and a segment can only
+    # end with the side stream joined -- the small weight gradients of the neck / head then stay on the launch stream instead of
+    # forking and joining once per layer (17.97 -> see profiles/r04_*_rccl_force_collectives.txt)
+    from .modules.step_plan import PlanRecorder
+    hold = sync and PlanRecorder.current is not None and not _capture_collectives(_SYNC_BN['group'])
+    prev_hold, WgradSide.hold_main = WgradSide.hold_main, hold or WgradSide.hold_main
+    dzs = []
+    for batch, args in zip(batches, operands):
+        dzs += ops.bn_silu_bwd_apply_group(*args, [grad_buf(m.mod.bn.weight) for m in batch], [grad_buf(m.mod.bn.bias) for m in batch],
+                                           [m.count for m in batch], count_devs=[m.count_dev for m in batch])
+    wg_done = False
+    if _group3x3(members, xs, ws):
+        with _wgrad_side(*dzs, *xs):                               # the weight gradients of the group: one launch on the side lane
+            wg_done = ops.conv3x3_group_wgrad(dzs, xs, [grad_buf(m.mod.conv.weight) for m in members])
+    plan, rounds = _dgrad_rounds([(m.x.data_ptr(), tuple(m.x.shape), m.stride) for m in members], [m.need_dx for m in members])
+    bufs = {}
+    for i, (m, dz, p) in enumerate(zip(members, dzs, plan)):
+        if not wg_done:
+            with _wgrad_side(dz, m.x):
+                ops.conv_nhwc_wgrad(dz, m.x, grad_buf(m.mod.conv.weight), None, stride=m.stride)
+        if p is not None and p[1] == 0:                            # the writer hands the shared buffer to autograd, the adders nothing
+            dxs[i] = bufs[p[0]] = ops._empty(tuple(m.x.shape), dz)
+    for rnd, idx in enumerate(rounds):
+        # the input gradients of one round write different buffers: one launch where the members share a channel geometry (head towers)
+        ms, dz_r, outs = [members[i] for i in idx], [dzs[i] for i in idx], [bufs[plan[i][0]] for i in idx]
+        done = False
+        if len(idx) > 1 and _group3x3(ms, dz_r, [m.conv_w.transpose(0, 1) for m in ms]):
+            done = ops.conv3x3_group_dgrad(dz_r, [m.conv_w for m in ms], [m.x.shape for m in ms], outs, [rnd > 0] * len(idx))
+        if not done:
+            for m, dz, out in zip(ms, dz_r, outs):
+                ops.conv_nhwc_dgrad(dz, m.conv_w, m.x.shape, stride=m.stride, out=out, accumulate=rnd > 0)
+    WgradSide.hold_main = prev_hold
+    return dxs
 
 
-class BaseConvGroupFn(Function):
-    """Several independent BaseConv layers evaluated as ONE autograd node so that their SyncBatchNorm statistics travel in one
-    all-reduce per direction (the three head levels' stems, the cls / reg tower layers of equal depth, conv1 / conv2 of a CSP
-    layer).  Only used when SyncBatchNorm is on; values are identical to separate ``BaseConvFn`` calls.
-    apply(mods, x_0..x_{n-1}, (conv_w, bn_w, bn_b) x n) -> y_0..y_{n-1}"""
+class ConvBNFn(Function):
+    """n >= 1 independent BaseConv layers in training as ONE autograd node: their SyncBatchNorm statistics travel in one all-reduce per
+    direction (the three head levels' stems, the cls / reg tower layers of equal depth, conv1 / conv2 of a CSP layer); values are
+    identical to one node per layer.  apply(mods, x_0..x_{n-1}, (conv_w, bn_w, bn_b) x n) -> (y_0..y_{n-1})"""
 
     @staticmethod
     def forward(ctx, mods, *tensors):
         n = len(mods)
-        xs, params = tensors[:n], tensors[n:]
-        need = any(ctx.needs_input_grad)
-        res = _conv_bn_fwd([(mods[i], xs[i], params[3 * i], params[3 * i + 1], params[3 * i + 2], mods[i].stride) for i in range(n)], need)
-        if need:
+        members = [ConvBN(mod, tensors[i], *tensors[n + 3 * i:n + 3 * i + 3], mod.stride) for i, mod in enumerate(mods)]
+        ys = _conv_bn_fwd(members)
+        if any(ctx.needs_input_grad):
             ctx.mods = mods
-            ctx.meta = [(r[1][3], r[1][4]) for r in res]
-            flat = []
-            for i, r in enumerate(res):
-                flat += [xs[i], r[1][0], r[1][1], r[1][2], params[3 * i], params[3 * i + 1], params[3 * i + 2]]
-            ctx.save_for_backward(*flat)
-        return tuple(r[0] for r in res)
+            ctx.counts = [(m.count, m.count_dev) for m in members]
+            ctx.save_for_backward(*[t for m in members for t in (m.x, m.z, m.mean, m.rstd, m.conv_w, m.bn_w, m.bn_b)])
+        return tuple(ys)
 
     @staticmethod
     def backward(ctx, *dys):
-        sv, mods = ctx.saved_tensors, ctx.mods
-        n = len(mods)
-        members = []
-        for i in range(n):
+        sv, members = ctx.saved_tensors, []
+        for i, (mod, (count, count_dev)) in enumerate(zip(ctx.mods, ctx.counts)):
             x, z, mean, rstd, conv_w, bn_w, bn_b = sv[7 * i:7 * i + 7]
-            members.append((mods[i], x, z, mean, rstd, conv_w, bn_w, bn_b, mods[i].stride, ctx.meta[i][0], ctx.meta[i][1],
-                            _rows(dys[i]), ctx.needs_input_grad[1 + i]))
-        dxs = _conv_bn_bwd(members)
-        return (None,) + tuple(dxs) + (None,) * (3 * n)
+            members.append(ConvBN(mod, x, conv_w, bn_w, bn_b, mod.stride, z, mean, rstd, count, count_dev,
+                                  dy=_rows(dys[i]), need_dx=ctx.needs_input_grad[1 + i]))
+        return (None, *_conv_bn_bwd(members), *(None,) * (3 * len(members)))
+
+
+def _conv_bn_apply(mods, xs):
+    return list(ConvBNFn.apply(tuple(mods), *xs, *[p for m in mods for p in (m.conv.weight, m.bn.weight, m.bn.bias)]))
+
+
+def base_conv(mod, x):
+    """BaseConv on an NHWC map: in evaluation conv + BN + SiLU as ONE fused kernel, in training the one-member group"""
+    if not mod.training:
+        return ops.conv_nhwc_fwd(x, mod.conv.weight, None, stride=mod.stride,
+                                 bn=(mod.bn.weight, mod.bn.bias, mod.bn.running_mean, mod.bn.running_var), bn_eps=mod.bn.eps)
+    return _conv_bn_apply([mod], [x])[0]
 
 
 def base_conv_group(mods, xs):
@@ -745,10 +748,7 @@ def base_conv_group(mods, xs):
     SyncBatchNorm, members of one channel geometry as one launch per kernel kind (``ops.conv3x3_group_*``), input gradients of members
     that read the same map summed inside the node; plain per-layer calls in evaluation."""
     if len(mods) > 1 and mods[0].training and (_sync_bn_on() or (torch.is_grad_enabled() and xs[0].is_cuda)):
-        params = []
-        for m in mods:
-            params += [m.conv.weight, m.bn.weight, m.bn.bias]
-        return list(BaseConvGroupFn.apply(tuple(mods), *xs, *params))
+        return _conv_bn_apply(mods, xs)
     return [m.forward_nhwc(x) for m, x in zip(mods, xs)]
 
 

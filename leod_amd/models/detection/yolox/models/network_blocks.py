@@ -32,7 +32,7 @@ class BaseConv(nn.Module):
         self.register_state_dict_pre_hook(lambda module, prefix, keep_vars: Fn.flush_bn_counters(module))
 
     def forward_nhwc(self, x):
-        return Fn.BaseConvFn.apply(self, x, self.conv.weight, self.bn.weight, self.bn.bias, self.stride, self.training)
+        return Fn.base_conv(self, x)
 
     def forward(self, x):
         """NCHW-logical in/out (reference signature)."""

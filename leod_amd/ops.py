@@ -748,13 +748,23 @@ BF16_GRADS = True          # 16-bit modes: du (and dqkv) stored as bf16
 STAT_REPLICAS = 32          # most copies of the BatchNorm (sum, sumsq) accumulators a conv epilogue spreads its atomics over
 
 
-def stat_replicas(rows: int) -> int:
-    """Replica count for a conv with ``rows`` output pixels: one per ~1280 rows (80 wave tiles), a power of two in [1, 32] -- the
-    consumer (bn_silu_fwd) folds the replicas in every workgroup, so small layers should not carry 32 of them."""
+def _replica_count(rows: int, per: int, cap: int) -> int:
+    """Copies of a per-channel accumulator block that the producers of ``rows`` rows spread their closing atomics over: one per ``per``
+    rows, a power of two in [1, cap] -- the consumer folds the copies in every workgroup, so small layers should not carry ``cap``."""
     r = 1
-    while r < STAT_REPLICAS and r * 1280 < rows:
+    while r < cap and r * per < rows:
         r *= 2
     return r
+
+
+def stat_replicas(rows: int) -> int:
+    """(sum, sumsq) copies for a conv with ``rows`` output pixels: one per ~1280 rows (80 wave tiles), at most 32; bn_silu_fwd folds them"""
+    return _replica_count(rows, 1280, STAT_REPLICAS)
+
+
+def bn_bwd_replicas(rows: int) -> int:
+    """(sum du, sum du*xhat) copies for bn_silu_bwd_reduce over ``rows`` rows: one per 2560 rows, at most 16; bn_silu_bwd_apply folds them"""
+    return _replica_count(rows, 2560, 16)
 
 
 class PackCache:
@@ -920,60 +930,65 @@ def conv3x3_group_ok(xs, ws) -> bool:
             and all(x.dim() == 4 and x.shape[-1] == w0.shape[1] and x.dtype is F32 and x.is_cuda for x in xs) and not _is_depthwise(w0, xs[0].shape[-1]))
 
 
+def _replicas(t) -> int:                      # copies in a statistics block: [R,2,N] -> R, a plain [2,N] -> 1
+    return t.shape[0] if t.dim() == 3 else 1
+
+
+def _conv3x3_group_tables(shapes, Cin, N, ws=None, pack_key=None):
+    """The tables of a grouped call that ``_conv3x3_group_routes_to`` has accepted: the members' B, H and W, behind -- for the entries that
+    read packed weights (``pack_key``: the PackCache key around (B, H, W)) -- the pack addresses and their valid flags."""
+    tables = [_int_array([sh[d] for sh in shapes]) for d in range(3)]
+    if pack_key is not None:
+        packs = [PackCache.get(w, pack_key[:1] + tuple(sh[:3]) + pack_key[1:], N * Cin * 9) for w, sh in zip(ws, shapes)]
+        tables = [_ptr_array([p for p, _ in packs]), _int_array([v for _, v in packs])] + tables
+    return tables
+
+
+def _ck_conv3x3_group(*tensors):
+    for t in tensors:
+        _ck(t, name='conv3x3_group')
+
+
 def conv3x3_group_fwd(xs, ws, colstats):
     """[x_k [B,H,W,Cin]], [w_k [N,Cin,3,3]], [colstats_k: zero-filled float64 [R,2,N]] -> [y_k] in ONE launch (stride 1, pad 1), or None
     where the direct kernel does not cover the geometry (run them singly)."""
-    n = len(xs)
-    for t in list(xs) + list(ws):
-        _ck(t, name='conv3x3_group')
+    _ck_conv3x3_group(*xs, *ws)
     for c in colstats:
         _ck(c, torch.float64, 'colstats')
     N, Cin = ws[0].shape[0], ws[0].shape[1]
-    if not _conv3x3_group_routes_to(110, 0, CF_PACK | CF_COLSTATS, [x.shape for x in xs], Cin, N):
+    shapes = [x.shape for x in xs]
+    if not _conv3x3_group_routes_to(110, 0, CF_PACK | CF_COLSTATS, shapes, Cin, N):
         return None
     ys = [_empty(tuple(x.shape[:3]) + (N,), x) for x in xs]
-    packs = [PackCache.get(w, ('fwd', x.shape[0], x.shape[1], x.shape[2], 1, False, False), N * Cin * 9) for x, w in zip(xs, ws)]
-    rc = _l().leod_conv3x3_group_fwd(n, _ptr_array(xs), _ptr_array(ws), _ptr_array(ys), _ptr_array(colstats),
-                                     _int_array([c.shape[0] if c.dim() == 3 else 1 for c in colstats]), _ptr_array([p for p, _ in packs]),
-                                     _int_array([v for _, v in packs]), _int_array([x.shape[0] for x in xs]), _int_array([x.shape[1] for x in xs]),
-                                     _int_array([x.shape[2] for x in xs]), Cin, N, _stream())
-    check(rc, 'conv3x3_group_fwd')
+    tables = _conv3x3_group_tables(shapes, Cin, N, ws, ('fwd', 1, False, False))
+    check(_l().leod_conv3x3_group_fwd(len(xs), _ptr_array(xs), _ptr_array(ws), _ptr_array(ys), _ptr_array(colstats),
+                                       _int_array([_replicas(c) for c in colstats]), *tables, Cin, N, _stream()), 'conv3x3_group_fwd')
     return ys
 
 
 def conv3x3_group_dgrad(dys, ws, x_shapes, outs, accumulate) -> bool:
     """outs[k] (+)= input gradient of conv(x_k, w_k) from dys[k] in ONE launch; False where not coverable (nothing was written)."""
-    n = len(dys)
-    for t in list(dys) + list(ws) + list(outs):
-        _ck(t, name='conv3x3_group')
+    _ck_conv3x3_group(*dys, *ws, *outs)
     N, Cin = ws[0].shape[0], ws[0].shape[1]
     if not _conv3x3_group_routes_to(110, 1, CF_PACK, x_shapes, Cin, N):
         return False
-    packs = [PackCache.get(w, ('dgrad', sh[0], sh[1], sh[2], 1), N * Cin * 9) for w, sh in zip(ws, x_shapes)]
-    rc = _l().leod_conv3x3_group_dgrad(n, _ptr_array(dys), _ptr_array(ws), _ptr_array(outs), _int_array([1 if a else 0 for a in accumulate]),
-                                       _ptr_array([p for p, _ in packs]), _int_array([v for _, v in packs]), _int_array([sh[0] for sh in x_shapes]),
-                                       _int_array([sh[1] for sh in x_shapes]), _int_array([sh[2] for sh in x_shapes]), Cin, N, _stream())
-    check(rc, 'conv3x3_group_dgrad')
+    tables = _conv3x3_group_tables(x_shapes, Cin, N, ws, ('dgrad', 1))
+    check(_l().leod_conv3x3_group_dgrad(len(dys), _ptr_array(dys), _ptr_array(ws), _ptr_array(outs), _int_array([1 if a else 0 for a in accumulate]),
+                                         *tables, Cin, N, _stream()), 'conv3x3_group_dgrad')
     return True
 
 
 def conv3x3_group_wgrad(dys, xs, dws) -> bool:
     """dws[k] += weight gradient of conv(x_k, w_k) from dys[k] (stride 1) in ONE launch (+ one reduce); False where not coverable."""
-    n = len(dys)
-    for t in list(dys) + list(xs) + list(dws):
-        _ck(t, name='conv3x3_group')
+    _ck_conv3x3_group(*dys, *xs, *dws)
     N, Cin = dws[0].shape[0], dws[0].shape[1]
-    if not _conv3x3_group_routes_to(500, 2, CF_WS, [x.shape for x in xs], Cin, N):
+    shapes = [x.shape for x in xs]
+    if not _conv3x3_group_routes_to(500, 2, CF_WS, shapes, Cin, N):
         return False
     sizes = [int(_l().leod_conv3x3_group_wgrad_workspace_floats(x.shape[0], x.shape[1], x.shape[2], Cin, N)) for x in xs]
-    ws = _empty((sum(sizes),), dys[0])
-    parts, off = [], 0
-    for sz in sizes:
-        parts.append(ws[off:off + sz])
-        off += sz
-    rc = _l().leod_conv3x3_group_wgrad(n, _ptr_array(dys), _ptr_array(xs), _ptr_array(dws), _ptr_array(parts), _int_array([x.shape[0] for x in xs]),
-                                       _int_array([x.shape[1] for x in xs]), _int_array([x.shape[2] for x in xs]), Cin, N, _stream())
-    check(rc, 'conv3x3_group_wgrad')
+    parts = list(_empty((sum(sizes),), dys[0]).split(sizes))
+    check(_l().leod_conv3x3_group_wgrad(len(dys), _ptr_array(dys), _ptr_array(xs), _ptr_array(dws), _ptr_array(parts),
+                                         *_conv3x3_group_tables(shapes, Cin, N), Cin, N, _stream()), 'conv3x3_group_wgrad')
     return True
 
 
@@ -992,76 +1007,76 @@ def conv_nhwc_wgrad(dy, x, dw, dbias=None, stride=1):
           'conv_nhwc_wgrad')
 
 
+def _bn_rows(zs, who):                        # -> (N, rows per layer) of the layers of one launch
+    N = zs[0].shape[-1]
+    if any(z.shape[-1] != N for z in zs):
+        raise LeodHipError(f'{who}: one channel count per launch')
+    return N, [z.numel() // N for z in zs]
+
+
+def _dy_stride(dy, N, who) -> int:            # row stride of a gradient the BN backward kernels read in place (``row_stride``)
+    ld = row_stride(dy, N)
+    if not ld:
+        raise LeodHipError(f'{who}: dy must be contiguous or a channel slice of a contiguous map')
+    _ck_dtype_dev(dy, F32, 'dy')
+    return ld
+
+
+def _count_devs(count_devs):                  # device-side row counts (SyncBatchNorm: the global image count); NULL when no layer has one
+    return None if count_devs is None or all(c is None for c in count_devs) else _ptr_array(count_devs)
+
+
 def bn_silu_fwd(z, colstats, w, b, run_mean, run_var, count, eps=1e-5, momentum=0.1, count_dev=None):
     _ck(z, name='z')
     _ck(colstats, torch.float64, 'colstats')
     N = z.shape[-1]
-    M = z.numel() // N
-    y = _empty(z.shape, z)
-    mean = _empty((N,), z)
-    rstd = _empty((N,), z)
-    rep = colstats.shape[0] if colstats.dim() == 3 else 1
-    check(_l().leod_bn_silu_fwd(_p(z), _p(colstats), rep, _p(w), _p(b), _p(y), _p(mean), _p(rstd), _p(run_mean), _p(run_var),
-                                 M, N, float(count), _p(count_dev), eps, momentum, _stream()), 'bn_silu_fwd')
+    y, mean, rstd = _empty(z.shape, z), _empty((N,), z), _empty((N,), z)
+    check(_l().leod_bn_silu_fwd(_p(z), _p(colstats), _replicas(colstats), _p(w), _p(b), _p(y), _p(mean), _p(rstd), _p(run_mean), _p(run_var),
+                                 z.numel() // N, N, float(count), _p(count_dev), eps, momentum, _stream()), 'bn_silu_fwd')
     return y, mean, rstd
 
 
-def _int_array(v):
-    return (ctypes.c_int * len(v))(*[int(a) for a in v])
-
-
-def _f64_array(v):
-    return (ctypes.c_double * len(v))(*[float(a) for a in v])
-
-
-def _f32_array(v):
-    return (ctypes.c_float * len(v))(*[float(a) for a in v])
-
-
 def bn_silu_fwd_group(zs, colstats, ws, bs, run_means, run_vars, counts, eps, momenta, count_devs=None):
-    """``bn_silu_fwd`` for n <= 8 layers of one channel count in ONE launch -> [(y, mean, rstd)]"""
-    n = len(zs)
-    N = zs[0].shape[-1]
-    for z_, c_ in zip(zs, colstats):
-        _ck(z_, name='z')
-        _ck(c_, torch.float64, 'colstats')
-        if z_.shape[-1] != N:
-            raise LeodHipError('bn_silu_fwd_group: one channel count per launch')
-    ys = [_empty(z_.shape, z_) for z_ in zs]
-    means = [_empty((N,), z_) for z_ in zs]
-    rstds = [_empty((N,), z_) for z_ in zs]
-    cd = None if count_devs is None or all(c is None for c in count_devs) else _ptr_array(count_devs)
-    check(_l().leod_bn_silu_fwd_group(n, _ptr_array(zs), _ptr_array(colstats), _int_array([c.shape[0] if c.dim() == 3 else 1 for c in colstats]),
+    """``bn_silu_fwd`` for 1 <= n <= 8 layers of one channel count in ONE launch -> [(y, mean, rstd)].  Here as in the two calls below a
+    lone layer goes to the scalar wrapper (the scalar C entry: same call table, same replayed plan, no host arrays)."""
+    if len(zs) == 1:
+        return [bn_silu_fwd(zs[0], colstats[0], ws[0], bs[0], run_means[0], run_vars[0], counts[0], eps=eps, momentum=momenta[0],
+                            count_dev=count_devs[0] if count_devs else None)]
+    N, rows = _bn_rows(zs, 'bn_silu_fwd_group')
+    for z, c in zip(zs, colstats):
+        _ck(z, name='z')
+        _ck(c, torch.float64, 'colstats')
+    ys, means, rstds = [_empty(z.shape, z) for z in zs], [_empty((N,), z) for z in zs], [_empty((N,), z) for z in zs]
+    check(_l().leod_bn_silu_fwd_group(len(zs), _ptr_array(zs), _ptr_array(colstats), _int_array([_replicas(c) for c in colstats]),
                                        _ptr_array(ws), _ptr_array(bs), _ptr_array(ys), _ptr_array(means), _ptr_array(rstds),
-                                       _ptr_array(run_means), _ptr_array(run_vars), _int_array([z_.numel() // N for z_ in zs]), N,
-                                       _f64_array(counts), cd, float(eps), _f32_array(momenta), _stream()), 'bn_silu_fwd_group')
+                                       _ptr_array(run_means), _ptr_array(run_vars), _int_array(rows), N, _f64_array(counts),
+                                       _count_devs(count_devs), float(eps), _f32_array(momenta), _stream()), 'bn_silu_fwd_group')
     return list(zip(ys, means, rstds))
 
 
 def bn_silu_bwd_reduce_group(dys, zs, means, rstds, ws, bs, outs):
-    n, N = len(zs), zs[0].shape[-1]
-    lds = []
-    for dy, z_ in zip(dys, zs):
-        ld = row_stride(dy, N)
-        if not ld or z_.shape[-1] != N:
-            raise LeodHipError('bn_silu_bwd_reduce_group: dy contiguous or a channel slice of a contiguous map; one channel count per launch')
-        _ck_dtype_dev(dy, F32, 'dy')
-        lds.append(ld)
-    check(_l().leod_bn_silu_bwd_reduce_group(n, _ptr_array(dys), _ptr_array(zs), _ptr_array(means), _ptr_array(rstds), _ptr_array(ws), _ptr_array(bs),
-                                              _ptr_array(outs), _int_array([o.shape[0] if o.dim() == 3 else 1 for o in outs]),
-                                              _int_array([z_.numel() // N for z_ in zs]), N, _int_array(lds), _stream()), 'bn_silu_bwd_reduce_group')
+    """``bn_silu_bwd_reduce`` for 1 <= n <= 8 layers of one channel count in ONE launch, into the zero-filled ``outs``"""
+    if len(zs) == 1:
+        bn_silu_bwd_reduce(dys[0], zs[0], means[0], rstds[0], ws[0], bs[0], out=outs[0])
+        return
+    N, rows = _bn_rows(zs, 'bn_silu_bwd_reduce_group')
+    lds = [_dy_stride(dy, N, 'bn_silu_bwd_reduce_group') for dy in dys]
+    check(_l().leod_bn_silu_bwd_reduce_group(len(zs), _ptr_array(dys), _ptr_array(zs), _ptr_array(means), _ptr_array(rstds), _ptr_array(ws),
+                                              _ptr_array(bs), _ptr_array(outs), _int_array([_replicas(o) for o in outs]), _int_array(rows), N,
+                                              _int_array(lds), _stream()), 'bn_silu_bwd_reduce_group')
 
 
 def bn_silu_bwd_apply_group(dys, zs, means, rstds, ws, bs, sums, dws, dbs, counts, count_devs=None):
-    n, N = len(zs), zs[0].shape[-1]
-    lds = [row_stride(dy, N) for dy in dys]
-    if not all(lds):
-        raise LeodHipError('bn_silu_bwd_apply_group: dy must be contiguous or a channel slice of a contiguous map')
-    dzs = [_empty(z_.shape, z_) for z_ in zs]
-    cd = None if count_devs is None or all(c is None for c in count_devs) else _ptr_array(count_devs)
-    check(_l().leod_bn_silu_bwd_apply_group(n, _ptr_array(dys), _ptr_array(zs), _ptr_array(means), _ptr_array(rstds), _ptr_array(ws), _ptr_array(bs),
-                                             _ptr_array(sums), _int_array([o.shape[0] if o.dim() == 3 else 1 for o in sums]), _ptr_array(dzs),
-                                             _ptr_array(dws), _ptr_array(dbs), _int_array([z_.numel() // N for z_ in zs]), N, _f64_array(counts), cd,
+    """``bn_silu_bwd_apply`` for 1 <= n <= 8 layers of one channel count in ONE launch -> [dz]"""
+    if len(zs) == 1:
+        return [bn_silu_bwd_apply(dys[0], zs[0], means[0], rstds[0], ws[0], bs[0], sums[0], dws[0], dbs[0], counts[0],
+                                  count_dev=count_devs[0] if count_devs else None)]
+    N, rows = _bn_rows(zs, 'bn_silu_bwd_apply_group')
+    lds = [_dy_stride(dy, N, 'bn_silu_bwd_apply_group') for dy in dys]
+    dzs = [_empty(z.shape, z) for z in zs]
+    check(_l().leod_bn_silu_bwd_apply_group(len(zs), _ptr_array(dys), _ptr_array(zs), _ptr_array(means), _ptr_array(rstds), _ptr_array(ws),
+                                             _ptr_array(bs), _ptr_array(sums), _int_array([_replicas(o) for o in sums]), _ptr_array(dzs),
+                                             _ptr_array(dws), _ptr_array(dbs), _int_array(rows), N, _f64_array(counts), _count_devs(count_devs),
                                              _int_array(lds), _stream()), 'bn_silu_bwd_apply_group')
     return dzs
 
@@ -1128,43 +1143,25 @@ def row_stride(t: torch.Tensor, N: int) -> int:
     return ld if (ld >= N and ld % 4 == 0 and t.storage_offset() % 4 == 0) else 0
 
 
-def bn_bwd_replicas(rows: int) -> int:
-    """Copies of the (sum du, sum du*xhat) block the workgroups of bn_silu_bwd_reduce spread their closing atomics over: one per
-    2560 rows, a power of two in [1, 16]; bn_silu_bwd_apply folds them in every workgroup."""
-    r = 1
-    while r < 16 and r * 2560 < rows:
-        r *= 2
-    return r
-
-
 def bn_silu_bwd_reduce(dy, z, mean, rstd, w, b, out=None):
     """out: zero-filled float64 [2,N] or [R,2,N] (R replicas, see ``bn_bwd_replicas``).
     dy: contiguous, or a channel slice of a wider contiguous map (see ``row_stride``) -- read in place with its row stride."""
     N = z.shape[-1]
     M = z.numel() // N
-    ld = row_stride(dy, N)
-    if not ld:
-        raise LeodHipError('bn_silu_bwd_reduce: dy must be contiguous or a channel slice of a contiguous map')
-    _ck_dtype_dev(dy, F32, 'dy')
+    ld = _dy_stride(dy, N, 'bn_silu_bwd_reduce')
     sums = StatArena.zeros((bn_bwd_replicas(M), 2, N), z.device) if out is None else out
     _ck(sums, torch.float64, 'sums')
-    rep = sums.shape[0] if sums.dim() == 3 else 1
-    check(_l().leod_bn_silu_bwd_reduce(_p(dy), _p(z), _p(mean), _p(rstd), _p(w), _p(b), _p(sums), rep, M, N, ld, _stream()),
+    check(_l().leod_bn_silu_bwd_reduce(_p(dy), _p(z), _p(mean), _p(rstd), _p(w), _p(b), _p(sums), _replicas(sums), M, N, ld, _stream()),
           'bn_silu_bwd_reduce')
     return sums
 
 
 def bn_silu_bwd_apply(dy, z, mean, rstd, w, b, sums, dw, db, count, count_dev=None):
     N = z.shape[-1]
-    M = z.numel() // N
-    ld = row_stride(dy, N)
-    if not ld:
-        raise LeodHipError('bn_silu_bwd_apply: dy must be contiguous or a channel slice of a contiguous map')
-    _ck_dtype_dev(dy, F32, 'dy')
+    ld = _dy_stride(dy, N, 'bn_silu_bwd_apply')
     dz = _empty(z.shape, z)
-    rep = sums.shape[0] if sums.dim() == 3 else 1
-    check(_l().leod_bn_silu_bwd_apply(_p(dy), _p(z), _p(mean), _p(rstd), _p(w), _p(b), _p(sums), rep, _p(dz), _p(dw), _p(db),
-                                       M, N, float(count), _p(count_dev), ld, _stream()), 'bn_silu_bwd_apply')
+    check(_l().leod_bn_silu_bwd_apply(_p(dy), _p(z), _p(mean), _p(rstd), _p(w), _p(b), _p(sums), _replicas(sums), _p(dz), _p(dw), _p(db),
+                                       z.numel() // N, N, float(count), _p(count_dev), ld, _stream()), 'bn_silu_bwd_apply')
     return dz
 
 
@@ -1475,6 +1472,18 @@ def _ptr_array(ts):
 
 def _long_array(v):
     return (ctypes.c_long * len(v))(*[int(x) for x in v])
+
+
+def _int_array(v):
+    return (ctypes.c_int * len(v))(*[int(a) for a in v])
+
+
+def _f64_array(v):
+    return (ctypes.c_double * len(v))(*[float(a) for a in v])
+
+
+def _f32_array(v):
+    return (ctypes.c_float * len(v))(*[float(a) for a in v])
 
 
 def multi_ok(ts) -> bool:

@@ -221,6 +221,54 @@ def test_head_grouped_launches_equal_per_layer(gpu, manifest, monkeypatch):
                 assert torch.equal(got[k], ref[k]), k
 
 
+@pytest.mark.parametrize('reads', [(0, 0, 0), (0, 0, 1)], ids=['three_sharers', 'two_sharers_one_unshared'])
+def test_base_conv_group_members_sharing_a_map(gpu, reads):
+    """Three BaseConv(48, 48, 3, 1) as one group (functions.base_conv_group) where several members read the SAME map -- their input
+    gradients are summed inside the node, the j-th reader of a map in round j of the input-gradient launches -- against the same three
+    layers called one by one: outputs and running statistics bit-identical, gradients equal to the order of their fp32 sums.  Three
+    readers of one map raised LEOD_ERR_ARG while the planner had two rounds (two adders of one buffer in one grouped launch)."""
+    from leod_amd import functions as Fn, ops
+    from leod_amd.models.detection.yolox.models.network_blocks import BaseConv
+
+    def rnd(shape, seed, scale=1.0):
+        return scale * torch.randn(shape, generator=torch.Generator().manual_seed(seed))
+
+    prev = ops.set_precision('bf16')
+    try:
+        assert ops.conv_route(1, 2, 5, 7, 48, 48, 3, 1, 1, ops.CF_PACK) == 110        # the direct kernel: the grouped dgrad takes these members
+
+        def run(grouped):
+            mods = []
+            for k in range(3):
+                m = BaseConv(48, 48, 3, 1)
+                with torch.no_grad():
+                    m.conv.weight.copy_(rnd(m.conv.weight.shape, 30 + k, 0.05))
+                    m.bn.weight.copy_(1 + 0.2 * rnd((48,), 40 + k))
+                    m.bn.bias.copy_(rnd((48,), 50 + k, 0.1))
+                mods.append(m.to(DEV).train())
+            maps = [rnd((2, 5, 7, 48), 60 + j).to(DEV).requires_grad_(True) for j in range(2)]
+            xs = [maps[j] for j in reads]
+            ys = Fn.base_conv_group(mods, xs) if grouped else [m.forward_nhwc(x) for m, x in zip(mods, xs)]
+            sum((y * rnd(y.shape, 70 + k, 0.1).to(DEV)).sum() for k, y in enumerate(ys)).backward()
+            torch.cuda.synchronize()
+            out = {f'y{k}': y.detach().clone() for k, y in enumerate(ys)}
+            for k, m in enumerate(mods):
+                out.update({f'b.{k}.mean': m.bn.running_mean.clone(), f'b.{k}.var': m.bn.running_var.clone()})
+                out.update({f'g.{k}.{n}': p.grad.clone() for n, p in m.named_parameters()})
+            out.update({f'gx{j}': x.grad.clone() for j, x in enumerate(maps) if j in reads})
+            return out
+
+        ref, got = run(False), run(True)
+    finally:
+        ops.set_precision(prev)
+    assert got.keys() == ref.keys() and len(ref) == 3 + 6 + 9 + len(set(reads))
+    for k in ref:
+        if k.startswith('g'):
+            torch.testing.assert_close(got[k], ref[k], rtol=2e-5, atol=1e-6, msg=k)
+        else:
+            assert torch.equal(got[k], ref[k]), k
+
+
 def test_backbone_backward_vs_oracle(gpu, manifest):
     """Gradients of a 3-step unrolled micro backbone (states carried, features of every stage used)."""
     det, sd, _ = build(manifest, 'micro', 5, 'small', micro=True, train=True)
