@@ -605,6 +605,30 @@ int leod_pixel_filter_query(long n_events, int H, int W, int* tile_events, int* 
 int leod_pixel_filter_scan(const void* records, long n_events, int H, int W, long burst_us, int burst_keep, long p_min_us, long p_max_us,
                            int lock, const unsigned char* mask, long* state, void* ws, long ws_bytes, void* marks, long marks_bytes,
                            long* io, leod_stream_t stream);
+/* Filter survey (csrc/k_survey.hip; the definitions and identities: DESIGN.md section 1) on the same records, in stream order, t
+ * non-decreasing: one pass that filters nothing and adds to integer histograms from which the counters of every filter above follow for
+ * a whole list of thresholds.  edges_us (HOST array): n_edges strictly increasing values, 0 <= e < 2^31, 1 <= n_edges <= 64 (= K);
+ * bin(d) = the number of edges < d.  Bounds and mask as above; any other event is a candidate.  p_min_us = p_max_us = 0: no flicker band
+ * (run[] is not touched); else 1 <= p_min_us <= p_max_us < 2^31.  At most 2^31 - 1 events per call.
+ * state: 8 + (5 * K + 262) + 4 * H * W longs on the device, updated in place, carried from chunk to chunk: [0] seen [1] candidates
+ *   [2] outside [3] masked [4] time of the first event seen (-1: none) [5] time of the last event seen (-1: none) [6] [7] 0; then
+ *   nb[K + 2] (d = t - the latest earlier candidate on one of the 8 neighbours; [K + 1]: none), same[K + 1] (d = t - t_prev where the
+ *   pixel's previous candidate has the same polarity), sec_on[K + 1], sec_off[K + 1] (c = the `same` bin of a candidate, c' = that of its
+ *   predecessor on the pixel, either INF where there is none: when c < c' and c < K, sec_on[c] += 1 and, if c' <= K, sec_off[c'] += 1),
+ *   period[K + 1] (d = t - t_edge at every rising edge with an edge before it), run[256] (n_per of the anti-flicker rule with lock = 255,
+ *   after every candidate; only with a band); then per pixel q four words: t_prev (time of the last candidate -- also the surface of the
+ *   activity filter; -1: never), t_edge (time of the last rising edge; -1: none), p_prev + 2 * c_prev (c_prev: the `same` bin of the last
+ *   candidate, 255 = INF), n_per.  A recording starts from zeros, [4] = [5] = -1 and {-1, -1, 510, 0} in every pixel.
+ * io: as for leod_event_filter_scan ([0] is not used).
+ * leod_survey_query (host only): *tile_events = records per tile of the sort, *digit_bits = key bits per pass of the sort
+ *   (ceil(ceil(log2(H * W + 1)) / digit_bits) passes), *ws_bytes = the workspace that takes n_events records in one piece,
+ *   *state_longs = the size of the state block (any may be NULL).
+ * leod_survey_events: ws (8-byte aligned): ws_bytes of scratch -- a chunk that needs more than it holds is cut at record boundaries into
+ *   pieces of whole tiles that fit (the workspace of one tile, leod_survey_query(1, ...), is the least); per piece four launches and three
+ *   per pass of the sort.  -1 for bad arguments (edges included). */
+int leod_survey_query(long n_events, int H, int W, int n_edges, int* tile_events, int* digit_bits, long* ws_bytes, long* state_longs);
+int leod_survey_events(const void* records, long n_events, int H, int W, const long* edges_us, int n_edges, long p_min_us, long p_max_us,
+                       const unsigned char* mask, long* state, void* ws, long ws_bytes, long* io, leod_stream_t stream);
 
 /* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
  * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,

@@ -1,4 +1,4 @@
-// What the record filters of the ingestion share (k_filter.hip, k_pixfilter.hip): the .dat record, the marks layout that
+// What the record filters of the ingestion and the filter survey share (k_filter.hip, k_pixfilter.hip, k_survey.hip): the .dat record, the marks layout that
 // leod_event_filter_emit reads (one class byte per record, padded to 8, then one u64 per tile: the offset of the tile's kept records;
 // class 0 is "kept"), the io block of a scan call, the wave / workgroup sums, and the three steps both filters take alike (classify,
 // tally_classes, scan_tiles).  Their __global__ kernels stay in the .hip files: separate translation units, no relocatable device code.
@@ -70,8 +70,21 @@ __device__ __forceinline__ void tally_classes(int c, unsigned long long* __restr
         atomicAdd(reinterpret_cast<unsigned long long*>(counters + threadIdx.x), (unsigned long long)lds_c[threadIdx.x]);
 }
 
+// What ONE lane does last for the piece [lo, hi): the times around a decrease in the piece, state[SEEN] += hi - lo, state[T_LAST] = the
+// last time.
+template <int SEEN, int T_LAST>
+__device__ __forceinline__ void close_piece(const Rec* __restrict__ rec, long lo, long hi, long* __restrict__ state, long* __restrict__ io) {
+    const long bad = io[IO_BAD];
+    if (bad >= lo && bad < hi) {
+        io[IO_T_BEFORE] = bad > 0 ? (long)rec[bad - 1].t : state[T_LAST];
+        io[IO_T_AT] = (long)rec[bad].t;
+    }
+    state[SEEN] += hi - lo;
+    if (hi > lo) state[T_LAST] = (long)rec[hi - 1].t;
+}
+
 // The body of a scan kernel, ONE workgroup, for the piece [lo, hi): the tiles' kept counts -> offsets behind the records emitted so far,
-// PASS tiles per pass; lane 0 then writes the times around a decrease in the piece, state[SEEN] += hi - lo, state[T_LAST] = the last time.
+// PASS tiles per pass; lane 0 then closes the piece (close_piece).
 template <int SEEN, int T_LAST>
 __device__ __forceinline__ void scan_tiles(const Rec* __restrict__ rec, long lo, long hi, long* __restrict__ state,
                                            unsigned long long* __restrict__ tile_off, long* __restrict__ io) {
@@ -89,13 +102,7 @@ __device__ __forceinline__ void scan_tiles(const Rec* __restrict__ rec, long lo,
     }
     if (threadIdx.x == 0) {
         io[IO_EMITTED] = (long)base;
-        const long bad = io[IO_BAD];
-        if (bad >= lo && bad < hi) {
-            io[IO_T_BEFORE] = bad > 0 ? (long)rec[bad - 1].t : state[T_LAST];
-            io[IO_T_AT] = (long)rec[bad].t;
-        }
-        state[SEEN] += hi - lo;
-        if (hi > lo) state[T_LAST] = (long)rec[hi - 1].t;
+        close_piece<SEEN, T_LAST>(rec, lo, hi, state, io);
     }
 }
 

@@ -6,11 +6,7 @@
 //   (a) pix_classify_kernel: class per record (outside / masked / candidate), sortedness, and the sort's input: key = the pixel y * W + x
 //       of a candidate (0 for any other record; the walk skips those by their class), value = the record's index;
 //   (b) a STABLE least-significant-digit radix sort of (key, index) on ceil(log2(H * W)) key bits, DIGIT bits a pass, three launches a
-//       pass: pix_hist_kernel (digit counts per sort tile -- SORT_TILES tiles of records, a workgroup takes them a tile a round --
-//       stored digit-major), pix_hist_scan_kernel (ONE workgroup: the exclusive sum over [digit][sort tile], which is where each sort
-//       tile's run of each digit starts), pix_scatter_kernel (rank of a record among its sort tile's earlier records of the same
-//       digit: the rounds before it, the waves before it in its round, and a wave ballot -- no rank is the return value of an atomic,
-//       so the permutation is the same in every run);
+//       pass (pixel_sort.hpp, shared with the filter survey of k_survey.hip: pix_hist_kernel, pix_hist_scan_kernel, pix_scatter_kernel);
 //   (c) pix_walk_kernel: the lane at the first sorted position of a pixel walks that pixel's run in index order with the pixel's state in
 //       registers, writes the class byte of every candidate and stores the state.  One lane walks a whole run: the cost is linear in
 //       the run, also when every event of the piece lies on one pixel;
@@ -23,21 +19,14 @@
 // Bounds: records are read below n_events only; x, y are compared with W, H before they index the mask or form a key, so a key is below
 // H * W and indexes the state block; the sort's values are the indices the classify pass wrote (lo <= index < hi); a scatter position
 // is compared with the piece's size before it is stored to; the entry points refuse buffers smaller than leod_pixel_filter_query reports.
-#include "filter_common.hpp"
+#include "pixel_sort.hpp"
 
 namespace {
 using namespace filt;
-constexpr int DIGIT = 8;                                         // key bits per sort pass
-constexpr int RADIX = 1 << DIGIT;                                // = BLOCK: lane d owns digit d of its tile's histogram
-constexpr int SCAN_PER_LANE = 16;                                // histogram entries a lane of the scan workgroup takes per pass
-constexpr int SORT_TILES = 8;                                    // tiles of records per workgroup of the sort: one digit count per 8 x 256 records
-constexpr long WS_TILE = (long)TILE * 16;                        // keys and indices, twice (ping-pong)
-constexpr long WS_HIST = (long)RADIX * 4;                        // the digit counts of one sort tile
 enum { C_FLICKER = 3, C_BURST = 4, N_CLASS = 5 };                // behind C_KEPT (a candidate until the walk decides), C_OUTSIDE, C_MASKED
 enum { S_SEEN = 0, S_KEPT, S_OUTSIDE, S_MASKED, S_FLICKER, S_BURST, S_T_LAST, S_HEAD = 8 };      // state block: include/leod_hip.h
 enum { P_T_PREV = 0, P_T_EDGE, P_PK, P_N_PER, P_LONGS };         // per pixel, behind the head
 enum { KEEP_FIRST = 0, KEEP_SECOND = 1, KEEP_FROM_SECOND = 2 };
-static_assert(RADIX == BLOCK, "one lane per digit");
 
 struct Rule { long tau; int keep; long p_min, p_max; int lock; };         // tau -1: the burst family is off; lock 0: flicker is off
 
@@ -53,88 +42,6 @@ __global__ __launch_bounds__(BLOCK) void pix_classify_kernel(const Rec* __restri
     cls[i] = (unsigned char)c;
     key[i - lo] = c == C_KEPT ? (unsigned)y * (unsigned)W + (unsigned)x : 0u;     // H * W <= 2^28
     idx[i - lo] = (unsigned)i;
-}
-
-// (b) digit counts of sort tile blockIdx.x -> hist[digit * n_stiles + sort tile]
-__global__ __launch_bounds__(BLOCK) void pix_hist_kernel(const unsigned* __restrict__ key, long n, int shift, long n_stiles,
-                                                         unsigned* __restrict__ hist) {
-    __shared__ unsigned lds_h[RADIX];
-    lds_h[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < SORT_TILES; ++r) {
-        const long j = ((long)blockIdx.x * SORT_TILES + r) * TILE + threadIdx.x;
-        if (j < n) atomicAdd(&lds_h[(key[j] >> shift) & (RADIX - 1)], 1u);        // a count: the sum is the same in any order
-    }
-    __syncthreads();
-    hist[(long)threadIdx.x * n_stiles + blockIdx.x] = lds_h[threadIdx.x];
-}
-
-// one workgroup: exclusive sum over the `total` entries of hist, in place
-__global__ __launch_bounds__(BLOCK) void pix_hist_scan_kernel(unsigned* __restrict__ hist, long total) {
-    __shared__ unsigned long long lds_s[BLOCK / 64];
-    unsigned long long base = 0;
-    for (long e0 = 0; e0 < total; e0 += (long)BLOCK * SCAN_PER_LANE) {
-        const long mine = e0 + (long)threadIdx.x * SCAN_PER_LANE;
-        unsigned v[SCAN_PER_LANE];
-        unsigned long long s = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_PER_LANE; ++k) {
-            v[k] = mine + k < total ? hist[mine + k] : 0u;
-            s += v[k];
-        }
-        unsigned long long sum;
-        unsigned long long off = base + block_scan_sum(s, sum, lds_s);
-#pragma unroll
-        for (int k = 0; k < SCAN_PER_LANE; ++k) {
-            if (mine + k < total) hist[mine + k] = (unsigned)off;                // below the piece's size, which is below 2^31
-            off += v[k];
-        }
-        base += sum;
-    }
-}
-
-// a record goes to: the start of its sort tile's run of its digit + its rank among the sort tile's earlier records of that digit
-__global__ __launch_bounds__(BLOCK) void pix_scatter_kernel(const unsigned* __restrict__ key_in, const unsigned* __restrict__ idx_in, long n,
-                                                            int shift, long n_stiles, const unsigned* __restrict__ hist,
-                                                            unsigned* __restrict__ key_out, unsigned* __restrict__ idx_out) {
-    __shared__ unsigned lds_w[BLOCK / 64][RADIX];                                // records of digit d in wave w, this round
-    __shared__ unsigned lds_run[RADIX];                                          // where the next record of digit d goes
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    lds_run[threadIdx.x] = hist[(long)threadIdx.x * n_stiles + blockIdx.x];
-    for (int w = 0; w < BLOCK / 64; ++w) lds_w[w][threadIdx.x] = 0;
-    for (int r = 0; r < SORT_TILES; ++r) {                                       // every lane takes every round: the barriers are uniform
-        __syncthreads();
-        const long j = ((long)blockIdx.x * SORT_TILES + r) * TILE + threadIdx.x;
-        const bool valid = j < n;
-        const unsigned k = valid ? key_in[j] : 0u, v = valid ? idx_in[j] : 0u;
-        const unsigned d = (k >> shift) & (RADIX - 1);
-        unsigned long long same = __ballot(valid);                               // the wave's lanes that hold a record of my digit
-#pragma unroll
-        for (int b = 0; b < DIGIT; ++b) {
-            const unsigned long long has = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? has : ~has;
-        }
-        const unsigned rank = (unsigned)__popcll(same & ((1ULL << lane) - 1ULL));
-        if (valid && rank == 0) lds_w[wave][d] = (unsigned)__popcll(same);       // the first lane of each digit: one store per digit
-        __syncthreads();
-        if (valid) {
-            unsigned before = 0;
-            for (int w = 0; w < wave; ++w) before += lds_w[w][d];
-            const long pos = (long)lds_run[d] + before + rank;
-            if (pos < n) {
-                key_out[pos] = k;
-                idx_out[pos] = v;
-            }
-        }
-        __syncthreads();
-        unsigned took = 0;                                                       // lane d owns column d: advance its run, clear its counts
-        for (int w = 0; w < BLOCK / 64; ++w) {
-            took += lds_w[w][threadIdx.x];
-            lds_w[w][threadIdx.x] = 0;
-        }
-        lds_run[threadIdx.x] += took;
-    }
 }
 
 // (c) the rule, steps (a) to (f) of DESIGN.md section 1, for the run of one pixel
@@ -192,23 +99,6 @@ __global__ __launch_bounds__(BLOCK) void pix_scan_kernel(const Rec* __restrict__
                                                          unsigned long long* __restrict__ tile_off, long* __restrict__ io) {
     scan_tiles<S_SEEN, S_T_LAST>(rec, lo, hi, state, tile_off, io);
 }
-
-int key_bits(int H, int W) {                                     // ceil(log2(H * W)): 0 for one pixel
-    int bits = 0;
-    while ((1L << bits) < (long)H * W) ++bits;
-    return bits;
-}
-long ws_of_tiles(long tiles) {                                   // a piece of so many tiles of records
-    return tiles * WS_TILE + (tiles + SORT_TILES - 1) / SORT_TILES * WS_HIST;
-}
-long ws_need(long n_events) {                                    // one piece that takes n_events records
-    const long tiles = (n_events + TILE - 1) / TILE;
-    return ws_of_tiles(tiles > 0 ? tiles : 1);
-}
-long tiles_of_ws(long ws_bytes) {                                // the largest piece the workspace takes: ws_of_tiles(it) <= ws_bytes
-    const long groups = ws_bytes / (SORT_TILES * WS_TILE + WS_HIST), rest = ws_bytes - groups * (SORT_TILES * WS_TILE + WS_HIST);
-    return groups * SORT_TILES + (rest >= WS_HIST ? (rest - WS_HIST) / WS_TILE : 0);
-}
 }  // namespace
 
 LEOD_API int leod_pixel_filter_query(long n_events, int H, int W, int* tile_events, int* tiles_per_pass, int* digit_bits, long* ws_bytes,
@@ -241,26 +131,16 @@ LEOD_API int leod_pixel_filter_scan(const void* records, long n_events, int H, i
     const Rec* rec = static_cast<const Rec*>(records);
     unsigned char* cls = static_cast<unsigned char*>(marks);
     unsigned long long* tile_off = reinterpret_cast<unsigned long long*>(cls + (n_events + 7) / 8 * 8);
-    unsigned* buf = static_cast<unsigned*>(ws);
-    unsigned* key[2] = {buf, buf + 2 * per};
-    unsigned* idx[2] = {buf + per, buf + 3 * per};
-    unsigned* hist = buf + 4 * per;                              // RADIX entries per sort tile of the piece
+    const SortWs s(ws, per);
     const Rule rule = {burst_us, burst_keep, p_min_us, p_max_us, lock};
-    const int bits = key_bits(H, W);
+    const int bits = key_bits((long)H * W);
     for (long lo = 0; lo < n_events; lo += per) {
         const long hi = lo + per < n_events ? lo + per : n_events;
-        const long n = hi - lo, n_tiles = (n + TILE - 1) / TILE, n_stiles = (n_tiles + SORT_TILES - 1) / SORT_TILES;
-        const dim3 sgrid((unsigned)n_stiles);
+        const long n = hi - lo, n_tiles = (n + TILE - 1) / TILE;
         const dim3 grid((unsigned)n_tiles), block(BLOCK);
-        hipLaunchKernelGGL(pix_classify_kernel, grid, block, 0, stream, rec, lo, hi, H, W, mask, state, cls, key[0], idx[0], io);
-        int cur = 0;
-        for (int shift = 0; shift < bits; shift += DIGIT, cur ^= 1) {
-            hipLaunchKernelGGL(pix_hist_kernel, sgrid, block, 0, stream, key[cur], n, shift, n_stiles, hist);
-            hipLaunchKernelGGL(pix_hist_scan_kernel, dim3(1), block, 0, stream, hist, (long)RADIX * n_stiles);
-            hipLaunchKernelGGL(pix_scatter_kernel, sgrid, block, 0, stream, key[cur], idx[cur], n, shift, n_stiles, hist, key[cur ^ 1],
-                               idx[cur ^ 1]);
-        }
-        hipLaunchKernelGGL(pix_walk_kernel, grid, block, 0, stream, rec, lo, hi, key[cur], idx[cur], rule, cls, state);
+        hipLaunchKernelGGL(pix_classify_kernel, grid, block, 0, stream, rec, lo, hi, H, W, mask, state, cls, s.key[0], s.idx[0], io);
+        const int cur = sort_pairs(s, n, bits, stream);
+        hipLaunchKernelGGL(pix_walk_kernel, grid, block, 0, stream, rec, lo, hi, s.key[cur], s.idx[cur], rule, cls, state);
         hipLaunchKernelGGL(pix_count_kernel, grid, block, 0, stream, lo, hi, cls, state, tile_off);
         hipLaunchKernelGGL(pix_scan_kernel, dim3(1), block, 0, stream, rec, lo, hi, state, tile_off, io);
         if (leod_launch_status() != LEOD_OK) return LEOD_ERR_LAUNCH;

@@ -1,6 +1,7 @@
 """Host side of the event noise filters of the ingestion (``ops.filter_events``, csrc/k_filter.hip; ``ops.pixel_filter_events``,
-csrc/k_pixfilter.hip; the rules: DESIGN.md section 1): the hot-pixel threshold, the pixel-mask file and the band of the anti-flicker
-filter.  NumPy only; nothing here touches the device."""
+csrc/k_pixfilter.hip; the rules: DESIGN.md section 1): the hot-pixel threshold, the pixel-mask file, the band of the anti-flicker
+filter, and the response curves of a filter survey (``ops.survey_events``, csrc/k_survey.hip).  NumPy only; nothing here touches the
+device."""
 from typing import Tuple
 
 import numpy as np
@@ -52,6 +53,33 @@ def hot_pixel_mask(counts, duration_us: int, max_rate_hz: int) -> np.ndarray:
     if floor >= np.iinfo(np.int64).max:
         return np.zeros(counts.shape, dtype=np.uint8)
     return (counts.astype(np.int64, copy=False) > floor).astype(np.uint8)
+
+
+def survey_responses(counters, edges_us) -> dict:
+    """The histograms of a filter survey (``ops.survey_counters``) -> the events each filter would REMOVE, applied
+    alone to the unfiltered stream: per edge of ``edges_us`` int64 arrays [K] ``denoise`` (``--denoise-us e``: unsupported events),
+    ``trail`` (``--trail-us e``), ``stc`` (``--stc-us e``), ``stc_cut_trail`` (``--stc-us e --stc-cut-trail``: burst events each), and
+    ``flicker`` int64 [256]: entry L is the number of events ``--flicker-lock L`` removes in the surveyed band (entry 0 is 0: no such
+    lock; all zeros where the survey had no band).  The five identities, in integers:
+        denoise[b]       = nb[K + 1] + sum(nb[b + 1 .. K])
+        trail[b]         = sum(same[.. b])
+        stc[b]           = candidates - sum(same[.. b])
+        stc_cut_trail[b] = candidates - (sum(sec_on[.. b]) - sum(sec_off[.. b]))
+        flicker[L]       = sum(run[L ..])"""
+    K = len(list(edges_us))
+    arr = {}
+    for name, n in (('nb', K + 2), ('same', K + 1), ('sec_on', K + 1), ('sec_off', K + 1), ('run', 256)):
+        a = np.asarray(counters[name])
+        if a.shape != (n,) or a.dtype.kind not in 'iu':
+            raise ValueError(f'counters[{name!r}]: {n} integers expected for {K} edges, got {a.dtype} {a.shape}')
+        arr[name] = a.astype(np.int64)
+    cand = int(counters['candidates'])
+    nb, same = arr['nb'], np.cumsum(arr['same'])[:K]
+    above = np.cumsum(nb[::-1])[::-1]                            # above[c] = sum(nb[c ..]), with nb[K + 1]: no earlier neighbour at all
+    second = (np.cumsum(arr['sec_on']) - np.cumsum(arr['sec_off']))[:K]
+    flicker = np.cumsum(arr['run'][::-1])[::-1].copy()
+    flicker[0] = 0
+    return dict(denoise=above[1:K + 1].copy(), trail=same.copy(), stc=cand - same, stc_cut_trail=cand - second, flicker=flicker)
 
 
 def check_pixel_mask(mask, sensor_hw: Tuple[int, int], what: str = 'pixel mask') -> np.ndarray:

@@ -1913,6 +1913,107 @@ def pixel_filter_counters(state):
     return _state_counters(state, _PIXFILTER_COUNTERS, PIXFILTER_STATE_HEAD, 'a per-pixel filter')
 
 
+# scratch of one piece of a chunk of ``survey_events``: the sort of csrc/pixel_sort.hpp, as for ``pixel_filter_events``
+SURVEY_WS_BYTES = PIXFILTER_WS_BYTES
+SURVEY_STATE_HEAD = 8
+SURVEY_PIXEL_LONGS = 4
+SURVEY_MAX_EDGES = 64
+SURVEY_RUN_BINS = 256
+_SURVEY_HEAD = dict(seen=0, candidates=1, outside=2, masked=3, t_first=4, t_last=5)
+
+
+def _ck_edges(edges_us):
+    """A strictly increasing list of 1 to 64 integers in [0, 2^31) -> the list."""
+    try:
+        edges = list(edges_us)
+    except TypeError:
+        raise LeodHipError(f'edges_us={edges_us!r}: a list of integers expected') from None
+    if not 1 <= len(edges) <= SURVEY_MAX_EDGES:
+        raise LeodHipError(f'edges_us: {len(edges)} edges; 1 to {SURVEY_MAX_EDGES} expected')
+    for e in edges:
+        if isinstance(e, bool) or not isinstance(e, int) or not 0 <= e < FILTER_TAU_LIMIT:
+            raise LeodHipError(f'edges_us: {e!r}; integers in [0, 2^31) expected')
+    for a, b in zip(edges[:-1], edges[1:]):
+        if not a < b:
+            raise LeodHipError(f'edges_us: {a} is followed by {b}; a strictly increasing list expected')
+    return edges
+
+
+def survey_query(n_events: int, height: int, width: int, n_edges: int):
+    """(records per tile of the sort, key bits per pass of the sort, workspace bytes that take ``n_events`` records in one piece, int64
+    words of the state block): the survey's own constants (csrc/k_survey.hip)."""
+    _ck_sensor(height, width)
+    te, db, wb, sl = (ctypes.c_int * 1)(), (ctypes.c_int * 1)(), (ctypes.c_long * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_survey_query(int(n_events), height, width, int(n_edges), te, db, wb, sl), 'survey_query')
+    return int(te[0]), int(db[0]), int(wb[0]), int(sl[0])
+
+
+def survey_events(records_u8, height, width, edges_us, flicker=None, state=None, pixel_mask=None, ws_bytes=None):
+    """A chunk of .dat records on the device (uint8 [n * 8] or [n, 8], stream order, t non-decreasing) -> the survey state with the chunk
+    added: nothing is filtered; the interval each filter's rule looks at is binned by ``edges_us`` (1 to 64 strictly
+    increasing integers in [0, 2^31); bin(d) = the number of edges < d) into integer histograms, from which ``survey_counters`` and
+    ``data.utils.event_filter.survey_responses`` give the exact count each filter would remove at every edge.  Events outside
+    [0, W) x [0, H) and events on a pixel where ``pixel_mask`` (uint8 or bool [H, W] on the device) is non-zero are counted and touch
+    nothing else.  ``flicker`` (None: the histogram ``run`` stays empty; (p_min_us, p_max_us) as ``event_filter.flicker_band`` makes it,
+    1 <= p_min_us <= p_max_us < 2^31): the band of the anti-flicker rule.
+    ``state`` (int64 on the device, layout in include/leod_hip.h: the head, the histograms, four words per pixel) carries the survey from
+    chunk to chunk, with the same edges and band: None starts a recording; the given tensor is not modified, the returned one is new.  A
+    chunk whose times decrease -- against the chunk before, too -- raises ``EventOrderError``.  ``ws_bytes`` (None:
+    ``SURVEY_WS_BYTES``) bounds the workspace: a chunk that needs more is cut into pieces that fit, which changes nothing but the
+    launches.  Per piece four launches and three per pass of the sort; one read-back (the order verdict)."""
+    _ck_sensor(height, width)
+    edges = _ck_edges(edges_us)
+    if flicker is None:
+        p_min = p_max = 0
+    else:
+        if not isinstance(flicker, (tuple, list)) or len(flicker) != 2:
+            raise LeodHipError(f'flicker={flicker!r}: None or two integers (p_min_us, p_max_us) expected')
+        p_min, p_max, _ = _ck_flicker((flicker[0], flicker[1], 1))
+    records_u8, n = _ck_records(records_u8)
+    dev = records_u8.device
+    _ck_pixel_mask(pixel_mask, height, width)
+    K = len(edges)
+    _, _, need, n_state = survey_query(n, height, width, K)
+    new = _filter_state(state, n_state, height, width)
+    if new is None:
+        n_hist = n_state - SURVEY_STATE_HEAD - SURVEY_PIXEL_LONGS * height * width
+        new = torch.cat([torch.tensor([0, 0, 0, 0, -1, -1, 0, 0], dtype=torch.int64), torch.zeros(n_hist, dtype=torch.int64),
+                         torch.tensor([-1, -1, 510, 0], dtype=torch.int64).repeat(height * width)]).to(dev)
+    least = survey_query(1, height, width, K)[2]
+    ws_bytes = SURVEY_WS_BYTES if ws_bytes is None else int(ws_bytes)
+    if ws_bytes < least:
+        raise LeodHipError(f'ws_bytes={ws_bytes}: at least {least} (one tile of records) expected')
+    ws_bytes = min(need, ws_bytes)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(dev)
+    check(_l().leod_survey_events(_p(records_u8), n, height, width, _long_array(edges), K, p_min, p_max, _p(pixel_mask), _p(new), _p(ws),
+                                  ws_bytes, _p(io), _stream()), 'survey_events')
+    _, bad, t_before, t_at = io.cpu().tolist()
+    if bad != _LONG_MAX:
+        raise EventOrderError(bad, t_before, t_at)
+    return new
+
+
+def survey_counters(state, n_edges):
+    """The head and the histograms of a survey state taken with ``n_edges`` edges (one read-back): the integers seen, candidates, outside,
+    masked, t_first, t_last, and numpy int64 arrays nb [K + 2], same, sec_on, sec_off, period [K + 1], run [256]."""
+    if isinstance(n_edges, bool) or not isinstance(n_edges, int) or not 1 <= n_edges <= SURVEY_MAX_EDGES:
+        raise LeodHipError(f'n_edges={n_edges!r}: an integer in [1, {SURVEY_MAX_EDGES}] expected')
+    K = n_edges
+    sizes = (('nb', K + 2), ('same', K + 1), ('sec_on', K + 1), ('sec_off', K + 1), ('period', K + 1), ('run', SURVEY_RUN_BINS))
+    head = SURVEY_STATE_HEAD + sum(s for _, s in sizes)
+    _ck(state, torch.int64, 'state')
+    if state.numel() < head or (state.numel() - head) % SURVEY_PIXEL_LONGS:
+        raise LeodHipError(f'state: a survey state of {n_edges} edges expected, got {tuple(state.shape)}')
+    host = state[:head].cpu().numpy()
+    out = {k: int(host[i]) for k, i in _SURVEY_HEAD.items()}
+    at = SURVEY_STATE_HEAD
+    for k, s in sizes:
+        out[k] = host[at:at + s].copy()
+        at += s
+    return out
+
+
 def event_pixel_counts(records_u8, height, width, counts=None):
     """Events per pixel of a chunk of .dat records on the device, added into ``counts`` (int64 [H, W] on the device; None: a new one of
     zeros) -> (counts, outside): ``outside`` (int64 [1] on the device) is the number of events with x >= W or y >= H, which are skipped.
