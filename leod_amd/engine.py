@@ -147,12 +147,7 @@ class TrainEngine:
         self._graph = torch.cuda.CUDAGraph(keep_graph=True) if plan else torch.cuda.CUDAGraph()
         side_in_graph, self.graph_side = self.graph_side, self.graph_side or plan
         ops.PackCache.invalidate()                                      # the capture must contain the weight packs of a step
-        ops.weight_shadow_pin(True)                                     # the recorded GEMMs read the shadow the recorded refresh writes
-        try:
-            with torch.cuda.graph(self._graph):
-                self._g_losses = self._graph_body()
-        finally:
-            ops.weight_shadow_pin(False)
+        self._capture_graph()
         self.graph_side = side_in_graph
         self._capturing = False
         self._plan = ops.LaunchPlan(self._graph, max_lanes) if plan else None
@@ -165,6 +160,18 @@ class TrainEngine:
         for bn, rm, rv in zip(bns, saved[4], saved[5]):
             bn.running_mean.copy_(rm); bn.running_var.copy_(rv)
         torch.cuda.synchronize()
+
+    def _capture_graph(self):
+        """The stream capture itself.  ``ops.LaunchPlan`` is told about it: a plan that the garbage collector finalises while the capture is
+        open (a dropped module's) is parked until it has ended instead of being destroyed inside it."""
+        ops.weight_shadow_pin(True)                                     # the recorded GEMMs read the shadow the recorded refresh writes
+        ops.LaunchPlan.capture_opened()
+        try:
+            with torch.cuda.graph(self._graph):
+                self._g_losses = self._graph_body()
+        finally:
+            ops.LaunchPlan.capture_closed()
+            ops.weight_shadow_pin(False)
 
     def _graph_body(self):
         losses, new_states = self._step_body(self._g_ev, self._g_labels, self._g_label_tb, self._g_first, self._g_states,

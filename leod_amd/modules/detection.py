@@ -25,7 +25,7 @@ except ImportError:
     _Base = th.nn.Module
 
 from leod_amd import ops
-from leod_amd.functions import WgradSide
+from leod_amd.functions import WgradSide, as_nchw
 from leod_amd.data.genx_utils.labels import ObjectLabels, SparselyBatchedObjectLabels
 from leod_amd.data.utils.packed import PackedBatch, batch_to_device
 from leod_amd.data.utils.types import DataType, DatasetSamplingMode, ObjDetOutput
@@ -64,7 +64,10 @@ class Module(_Base):
         # timestep-major loop over ``forward_backbone`` (same values, ~5x more and smaller launches)
         self.time_batched = True          # stage-major time-batched schedule (False: the reference's timestep-major loop, for state inspection)
         self.wgrad_side = True            # weight-gradient kernels on a side HIP stream (False: on the launch stream)
-        self.plan_head_eager = False      # option for N > 1: planned backbone, eager PAFPN + head (see _head_eager)
+        # option for N > 1: planned backbone, eager PAFPN + head.  Every SyncBatchNorm exchange inside a captured head is a plan segment
+        # boundary (the backbone has no BatchNorm); the eager head is slightly faster there at 2.5x the host time per step, so the captured
+        # head stays the default (figures: INTEGRATION.md)
+        self.plan_head_eager = False
         self._row_idx_cache: Dict[Any, th.Tensor] = {}
         # launch plans (modules/step_plan.py): a training-step geometry seen twice is captured once and replayed from C afterwards --
         # this build's counterpart of the reference's ``backbone.compile`` switch (torch.compile(mode='reduce-overhead') = CUDA graphs,
@@ -169,19 +172,11 @@ class Module(_Base):
         assert L > 0
         if self.mode_2_batch_size[mode] is None:
             self.mode_2_batch_size[mode] = B
-        else:
-            assert self.mode_2_batch_size[mode] == B
-        hw = tuple(ev_seq[0].shape[-2:])
         if self.mode_2_hw[mode] is None:
-            self.mode_2_hw[mode] = hw
-        else:
-            assert self.mode_2_hw[mode] == hw
+            self.mode_2_hw[mode] = tuple(ev_seq[0].shape[-2:])
+        self._assert_static_shape(mode, B, tuple(ev_seq[0].shape[-2:]))
         prev_states = rnn.get_states(worker_id=worker_id)
-        obj_labels, where = [], []
-        for tidx in range(L):
-            cur, idx = labels_seq[tidx].get_valid_labels_and_batch_indices(**(ignore_kwargs or {}))
-            obj_labels.extend(cur)
-            where.extend((tidx, b) for b in idx)
+        obj_labels, where = self._labelled_frames(labels_seq, ignore_kwargs)
         in_features = self.mdl.fpn.in_features
         if self.time_batched:
             ev = self._stack_frames(ev_seq)
@@ -205,6 +200,27 @@ class Module(_Base):
             feats = selector.get_batched_backbone_features()
         rnn.save_states_and_detach(worker_id=worker_id, states=states)
         return feats, obj_labels, where, B
+
+    def _assert_static_shape(self, mode: Mode, B: int, hw) -> None:
+        """constant batch size and resolution per mode (reference asserts, detection.py:176-179,196-199)"""
+        assert self.mode_2_batch_size[mode] == B and self.mode_2_hw[mode] == hw
+
+    @staticmethod
+    def _labelled_frames(labels_seq, ignore_kwargs=None):
+        """-> (the valid ObjectLabels of the sequence in (t, b) order, their [(t, b)])"""
+        obj_labels, where = [], []
+        for tidx in range(len(labels_seq)):
+            cur, idx = labels_seq[tidx].get_valid_labels_and_batch_indices(**(ignore_kwargs or {}))
+            obj_labels.extend(cur)
+            where.extend((tidx, b) for b in idx)
+        return obj_labels, where
+
+    def _step_output(self, losses, B: int, log: bool):
+        """What ``training_step`` returns, logged through Lightning where there is one."""
+        output = {'loss': losses['loss'], 'log_dict': {f'{mode_2_string[Mode.TRAIN]}/{k}': v for k, v in losses.items()}}
+        if hasattr(self, 'log_dict') and log and _Base is not th.nn.Module:  # pragma: no cover
+            self.log_dict(output['log_dict'], on_step=True, on_epoch=True, batch_size=B, sync_dist=False, rank_zero_only=True)
+        return output
 
     def _upload_pinned(self, t: th.Tensor, device) -> th.Tensor:
         """Host tensor -> device through a ring of 4 pinned staging buffers (asynchronous copy on the launch stream; a
@@ -254,117 +270,78 @@ class Module(_Base):
         assert losses is not None and 'loss' in losses
         # the weight-gradient kernels of the backward pass that follows run on a side HIP stream until the optimiser joins it
         WgradSide.active = self.wgrad_side and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing()
-        output = {'loss': losses['loss'],
-                  'log_dict': {f'{mode_2_string[Mode.TRAIN]}/{k}': v for k, v in losses.items()}}
-        if hasattr(self, 'log_dict') and log and _Base is not th.nn.Module:  # pragma: no cover
-            self.log_dict(output['log_dict'], on_step=True, on_epoch=True, batch_size=B, sync_dist=False, rank_zero_only=True)
-        return output
+        return self._step_output(losses, B, log)
 
     def _training_step_planned(self, data, worker_id: int, ign, log: bool):
         """The same step through a launch plan (modules/step_plan.py), or None when this batch has to run eagerly: the first
         occurrence of its geometry, host-resident frames, no labelled frame, or a geometry whose capture failed."""
-        from .step_plan import PlanLossFn, BackbonePlan, LOSS_KEYS
-        ev_seq = data[DataType.EV_REPR]
+        from .step_plan import PlanLossFn, EagerHeadGate, CAPTURE, EAGER, LOSS_KEYS
         labels_seq = data[DataType.OBJLABELS_SEQ]
         is_first = data[DataType.IS_FIRST_SAMPLE]
-        L, B = len(ev_seq), len(labels_seq[0])
-        obj_labels, where = [], []
-        for tidx in range(L):
-            cur, idx = labels_seq[tidx].get_valid_labels_and_batch_indices(**ign)
-            obj_labels.extend(cur)
-            where.extend((tidx, b) for b in idx)
+        B = len(labels_seq[0])
+        obj_labels, where = self._labelled_frames(labels_seq, ign)
         if not where:
             return None
-        ev = self._stack_frames(ev_seq)
+        ev = self._stack_frames(data[DataType.EV_REPR])
+        device = ev.device
         labels_yolox = ObjectLabels.get_labels_as_batched_tensor(obj_label_list=obj_labels, format_='yolox').to(th.float32)
         plans = self._plans
         key = plans.key_of(ev)
-        hit = plans.lookup(key)
-        if hit is None:
+        bb = plans.lookup(key)
+        if bb is None:
             return None
         mode = Mode.TRAIN
-        hw = tuple(ev.shape[-2:])
         if self.mode_2_batch_size[mode] is None or self.mode_2_hw[mode] is None:
-            return None                                  # the eager step records them (reference asserts, detection.py:176-179,196-199)
-        assert self.mode_2_batch_size[mode] == B and self.mode_2_hw[mode] == hw
+            return None                                  # the eager step records them
+        self._assert_static_shape(mode, B, tuple(ev.shape[-2:]))
         rnn = self.mode_2_rnn_states[mode]
         fresh = False                                    # a plan of this step was captured in this very call
-        if hit == 'capture':
+        if bb is CAPTURE:
             like = rnn.get_states(worker_id) or next(iter(rnn.states.values()), None)
             if like is None:
                 return None
-            hit = plans.build(key, self, ev, like, self.wgrad_side)
-            if hit is None:
+            bb = plans.build(key, self, ev, like, self.wgrad_side)
+            if bb is None:
                 return None
             fresh = True
-        bb: BackbonePlan = hit
-        if self._head_eager():
-            return self._planned_backbone_eager_head(bb, plans, fresh, ev, labels_yolox, where, is_first, worker_id, rnn, B, log)
-        # the data-dependent part: PAFPN + head for THIS labelled-frame count (captured the first time the count is seen; nothing has been
-        # executed yet, so a failed capture simply leaves the step to the eager path)
-        hkey, nmax_pad = plans.head_key_of(len(where), labels_yolox.shape[1])
-        hd = bb.head(hkey)
-        if hd is None:
-            hd = plans.build_head(bb, hkey, self, len(where), nmax_pad, self.wgrad_side)
-            fresh = True
-        if hd is None or hd == 'eager':
-            return None
-        self.started_training = True
-        rows_host = tuple(t * B + b for t, b in where)
-        bb.load_states(rnn, worker_id)
-        bb.stage_inputs(ev, rows_host, self._row_index(rows_host + (-1,) * (bb.n_max - len(rows_host)), ev.device), is_first)
-        hd.stage_labels(labels_yolox)
-        bb.run_forward()
-        hd.run_forward()
-        rnn.save_states_and_detach(worker_id=worker_id, states=bb.states)
-        plans.steps += 1
-        plans.replays += 0 if fresh else 1
-        if plans.anchor is None or plans.anchor.device != ev.device:
-            plans.anchor = th.zeros(1, device=ev.device, requires_grad=True)
-        entry = hd
-        out6 = entry.losses6.clone()                     # the static loss buffer is overwritten by the next replay
-        loss = PlanLossFn.apply(bb, hd, plans.anchor, out6[0])
-        losses = {k: out6[i] for i, k in enumerate(LOSS_KEYS)}
-        losses['loss'] = loss
-        output = {'loss': loss, 'log_dict': {f'{mode_2_string[Mode.TRAIN]}/{k}': v for k, v in losses.items()}}
-        if hasattr(self, 'log_dict') and log and _Base is not th.nn.Module:  # pragma: no cover
-            self.log_dict(output['log_dict'], on_step=True, on_epoch=True, batch_size=B, sync_dist=False, rank_zero_only=True)
-        return output
-
-    def _head_eager(self) -> bool:
-        """Planned backbone + eager head (``module.plan_head_eager = True``): an option for N > 1, where every SyncBatchNorm exchange inside a captured
-        head is a plan segment boundary (the backbone has no BatchNorm: its plans stay whole apart from the gradient buckets).  Measured
-        with every collective issued on a one-rank RCCL communicator (profiles/r05_p_rccl_force_collectives.txt): 16.98 ms per step against
-        17.3-17.4 with the captured head and 16.3-16.5 all-eager (15.4 without collectives) -- but 10.5 instead of 4.1 ms of host time per
-        step, i.e. it depends on the host the way eager launches do; the captured head stays the default."""
-        return bool(self.plan_head_eager)
-
-    def _planned_backbone_eager_head(self, bb, plans, fresh, ev, labels_yolox, where, is_first, worker_id, rnn, B, log):
-        from .step_plan import EagerHeadGate
-        from leod_amd import functions as Fn
-        device = ev.device
-        self.started_training = True
+        hd = None                                        # stays None with ``plan_head_eager``: planned backbone, eager PAFPN + head
+        if not self.plan_head_eager:
+            # the data-dependent part: PAFPN + head for THIS labelled-frame count (captured the first time the count is seen; nothing has been
+            # executed yet, so a failed capture simply leaves the step to the eager path)
+            hkey, nmax_pad = plans.head_key_of(len(where), labels_yolox.shape[1])
+            hd = bb.head(hkey)
+            if hd is None:
+                hd = plans.build_head(bb, hkey, self, len(where), nmax_pad, self.wgrad_side)
+                fresh = True
+            if hd is None or hd is EAGER:
+                return None
         rows_host = tuple(t * B + b for t, b in where)
         bb.load_states(rnn, worker_id)
         bb.stage_inputs(ev, rows_host, self._row_index(rows_host + (-1,) * (bb.n_max - len(rows_host)), device), is_first)
-        if labels_yolox.device != device:
+        if hd is not None:
+            hd.stage_labels(labels_yolox)
+        elif labels_yolox.device != device:
             labels_yolox = self._upload_pinned(labels_yolox, device)
         bb.run_forward()
+        if hd is not None:
+            hd.run_forward()
         rnn.save_states_and_detach(worker_id=worker_id, states=bb.states)
         plans.steps += 1
         plans.replays += 0 if fresh else 1
         if plans.anchor is None or plans.anchor.device != device:
             plans.anchor = th.zeros(1, device=device, requires_grad=True)
-        ops.StatArena.begin_step(device)             # the eager head's BatchNorm statistic accumulators (the backbone plan has its own arena)
-        in_features = tuple(self.mdl.fpn.in_features)
-        sel = EagerHeadGate.apply(bb, plans.anchor, self._row_index(rows_host, device), *in_features)
-        _, losses = self.mdl.forward_detect(backbone_features={k: Fn.as_nchw(v) for k, v in zip(in_features, sel)},
-                                            targets=labels_yolox.to(torch.float32))
-        WgradSide.active = self.wgrad_side and torch.is_grad_enabled()
-        output = {'loss': losses['loss'], 'log_dict': {f'{mode_2_string[Mode.TRAIN]}/{k}': v for k, v in losses.items()}}
-        if hasattr(self, 'log_dict') and log and _Base is not th.nn.Module:  # pragma: no cover
-            self.log_dict(output['log_dict'], on_step=True, on_epoch=True, batch_size=B, sync_dist=False, rank_zero_only=True)
-        return output
+        if hd is not None:
+            out6 = hd.losses6.clone()                    # the static loss buffer is overwritten by the next replay
+            losses = {k: out6[i] for i, k in enumerate(LOSS_KEYS)}
+            losses['loss'] = PlanLossFn.apply(bb, hd, plans.anchor, out6[0])
+        else:
+            ops.StatArena.begin_step(device)             # the eager head's BatchNorm statistic accumulators (the backbone plan has its own arena)
+            in_features = tuple(self.mdl.fpn.in_features)
+            sel = EagerHeadGate.apply(bb, plans.anchor, self._row_index(rows_host, device), *in_features)
+            _, losses = self.mdl.forward_detect(backbone_features={k: as_nchw(v) for k, v in zip(in_features, sel)},
+                                                targets=labels_yolox.to(torch.float32))
+            WgradSide.active = self.wgrad_side and torch.is_grad_enabled()
+        return self._step_output(losses, B, log)
 
     def backward(self, loss: th.Tensor, *args, **kwargs) -> None:
         """Lightning's backward hook (and what ``leod_amd.optim.fit_step`` calls)."""

@@ -17,6 +17,8 @@ than one rank with SyncBatchNorm (collectives between the kernels), or a graph n
 Measured (RVT-S Gen1 bs 8 L 21, bf16 mode, profiles/r04_*): hipGraphLaunch of the same captures costs 8 us of host time per node and
 loses the side stream; the plans make the step independent of the host (16.5 ms on a host where the eager step is 17.7 ms).
 """
+import contextlib
+import enum
 import os
 import warnings
 from typing import Any, Dict, List, Optional, Tuple
@@ -33,8 +35,17 @@ LOSS_KEYS = ('loss', 'iou_loss', 'conf_loss', 'cls_loss', 'l1_loss', 'num_fg')
 NMAX_PAD = 8          # label rows are padded to a multiple of this (all-zero rows are "no box" to SimOTA / the loss, yolo_head.py:437-441)
 
 
+# What the cache holds or answers in place of a plan, compared by identity.  SEEN (entry): the geometry ran once, eagerly, its next step is captured;
+# EAGER (entry, head entry): its capture failed or its plan was evicted, such steps stay eager; CAPTURE (answer of ``lookup``): second sight.
+SEEN, EAGER, CAPTURE = enum.Enum('Mark', 'SEEN EAGER CAPTURE')
+
+
 def _flat(states) -> List[th.Tensor]:
     return [t for pair in states for t in pair]
+
+
+def _to_end(d: dict, key):
+    d[key] = d.pop(key)                                      # most recently used last
 
 
 class PlanRecorder:
@@ -113,13 +124,12 @@ class PlanRecorder:
             plan.join()
 
     def info(self):
-        k = sum(p.info['kernels'] for p, _ in self.segments if p is not None)
-        return {'kernels': k, 'memsets': sum(p.info['memsets'] for p, _ in self.segments if p is not None),
-                'memcpys': sum(p.info['memcpys'] for p, _ in self.segments if p is not None),
-                'lanes': max([p.info['lanes'] for p, _ in self.segments if p is not None] or [0]),
-                'waits': sum(p.info['waits'] for p, _ in self.segments if p is not None),
-                'segments': len(self.segments), 'callbacks': sum(1 for _, c in self.segments if c is not None),
-                'collectives': sum(p.info.get('collectives', 0) for p, _ in self.segments if p is not None)}
+        infos = [p.info for p, _ in self.segments if p is not None]
+        def total(k):
+            return sum(i.get(k, 0) for i in infos)
+        return {'kernels': total('kernels'), 'memsets': total('memsets'), 'memcpys': total('memcpys'),
+                'lanes': max([i['lanes'] for i in infos] or [0]), 'waits': total('waits'), 'segments': len(self.segments),
+                'callbacks': sum(1 for _, c in self.segments if c is not None), 'collectives': total('collectives')}
 
     def close(self):
         for p, _ in self.segments:
@@ -128,12 +138,93 @@ class PlanRecorder:
         self.segments = []
 
 
+class StepCapture:
+    """The capture protocol of one plan, stated once: its forward and its backward pass are recorded, not executed, as two ``PlanRecorder``
+    captures in ONE memory pool on a stream of their own.  ``BackbonePlan.capture`` and ``HeadPlan.capture`` supply the bodies of
+    ``with step_capture(...) as cap: with cap.forward(): ...  with cap.backward(): ...`` and what is theirs alone.  The order is load-bearing:
+
+    * enter: the plan's private ``StatArena`` buffer is swapped in, ``GradBuckets.current`` and ``WgradSide.active`` are saved,
+      ``PackCache.invalidate()`` (the capture must contain the weight packs of a step), a fresh capture stream waits for the current one, the
+      device is synchronised.  Up to the exit everything runs with gradients enabled on the capture stream, also what happens between the
+      two captures (ordinary memory: the backbone allocates its gradient slots there).
+    * ``forward(first)``: the forward recorder is ``PlanRecorder.current``; begin; ``first()`` (the backbone's weight-shadow refresh), then
+      ``StatArena.begin_step`` are the first recorded work; body; end.
+    * ``backward()``: a second recorder in the SAME pool is ``PlanRecorder.current``; begin; ``WgradSide.active`` is the step's setting during
+      the body and False after it, also when it raises; end; ``StatArena.high`` -> ``arena_high`` while the plan's arena is still installed.
+    * an exception anywhere: every capture still open is ended ON the capture stream (a capturing graph aborts the process in its
+      destructor), both recorders are closed.
+    * every exit: ``PlanRecorder.current`` is None, the current stream waits for the capture stream, arena, buckets and ``WgradSide.active``
+      are what they were, ``PackCache.invalidate()`` again (nothing was executed: the pack buffers do not hold what the cache believes)."""
+
+    def __init__(self, device, max_lanes: int, wgrad_side: bool, pool=None):
+        self.device, self.max_lanes, self.wgrad_side = device, max_lanes, wgrad_side
+        self.fwd, self.bwd, self.arena_high = PlanRecorder(max_lanes, pool=pool), None, 0
+
+    @contextlib.contextmanager
+    def forward(self, first=None):
+        PlanRecorder.current = self.fwd
+        self.fwd.begin()
+        if first is not None:
+            first()
+        ops.StatArena.begin_step(self.device)
+        yield
+        self.fwd.end()
+
+    @contextlib.contextmanager
+    def backward(self):
+        self.bwd = PlanRecorder(self.max_lanes, pool=self.fwd.pool)
+        PlanRecorder.current = self.bwd
+        self.bwd.begin()
+        Fn.WgradSide.active = self.wgrad_side
+        try:
+            yield
+        finally:
+            Fn.WgradSide.active = False
+        self.bwd.end()
+        self.arena_high = ops.StatArena.high
+
+    def abort(self, stream):
+        with th.cuda.stream(stream):
+            for rec in filter(None, (self.fwd, self.bwd)):
+                if rec.graph is not None:
+                    with contextlib.suppress(Exception):
+                        Fn.WgradSide.join()
+                        rec._capture_end()
+                rec.close()
+
+
+@contextlib.contextmanager
+def step_capture(device, arena: th.Tensor, max_lanes: int, wgrad_side: bool, pool=None):
+    from leod_amd.parallel import GradBuckets
+    saved_arena, saved_buckets, saved_side = ops.StatArena.swap(arena), GradBuckets.current, Fn.WgradSide.active
+    ops.PackCache.invalidate()
+    stream = None
+    try:
+        stream = th.cuda.Stream(device=device)
+        stream.wait_stream(th.cuda.current_stream())
+        th.cuda.synchronize()
+        cap = StepCapture(device, max_lanes, wgrad_side, pool)
+        try:
+            with th.enable_grad(), th.cuda.stream(stream):
+                yield cap
+        except BaseException:
+            cap.abort(stream)
+            raise
+    finally:
+        PlanRecorder.current = None
+        if stream is not None:
+            th.cuda.current_stream().wait_stream(stream)
+        ops.StatArena.swap(*saved_arena)
+        GradBuckets.current, Fn.WgradSide.active = saved_buckets, saved_side
+        ops.PackCache.invalidate()
+
+
 class PlanLossFn(Function):
     """The loss of a replayed step as an autograd leaf-to-loss edge: ``forward`` has already happened (the forward plans), ``backward``
     hands the seed gradient to the captured backward passes and launches them.  Parameter gradients land in the flat gradient buffer as
     in the eager step (the captured weight-gradient kernels accumulate into the same addresses).  The plans hold ONE step's activations:
     a second forward of the same geometry before this backward (two losses summed, ``retain_graph`` replays) would differentiate the first
-    loss with the second step's activations -- refused loudly."""
+    loss with the second step's activations -- refused loudly (``BackbonePlan.claim``)."""
 
     @staticmethod
     def forward(ctx, bb, hd, anchor, loss):
@@ -143,11 +234,7 @@ class PlanLossFn(Function):
     @staticmethod
     def backward(ctx, g):
         bb, hd = ctx.bb, ctx.hd
-        if bb.uses != ctx.gen or bb.consumed == ctx.gen or hd.fwd is None or bb.fwd is None:
-            raise RuntimeError('leod_amd launch plans: backward() of a planned training step whose activations are gone (another '
-                               'training_step of the same geometry ran before this backward, backward ran twice, or the plan was evicted); '
-                               'run such steps with Module.plan_mode = False')
-        bb.consumed = ctx.gen
+        bb.claim(ctx.gen, hd.fwd)
         hd.run_backward(g)
         bb.run_backward()
         hd.bwd.join()
@@ -170,11 +257,7 @@ class EagerHeadGate(Function):
     @staticmethod
     def backward(ctx, *grads):
         bb = ctx.bb
-        if bb.uses != ctx.gen or bb.consumed == ctx.gen or bb.fwd is None:
-            raise RuntimeError('leod_amd launch plans: backward() of a planned training step whose activations are gone (another '
-                               'training_step of the same geometry ran before this backward, backward ran twice, or the plan was evicted); '
-                               'run such steps with Module.plan_mode = False')
-        bb.consumed = ctx.gen
+        bb.claim(ctx.gen)
         dst, src = [], []
         for k, g in zip(ctx.stages, grads):
             if g is None:
@@ -213,52 +296,21 @@ class HeadPlan:
         in_features = tuple(mdl.fpn.in_features)
         mods = [m for m in mdl.modules() if hasattr(m, 'bn_calls_pending')]
         pending0 = [m.bn_calls_pending for m in mods]
-        saved_arena = ops.StatArena.swap(bb.head_arena)
-        from leod_amd.parallel import GradBuckets
-        saved_buckets = GradBuckets.current
-        saved_side = Fn.WgradSide.active
-        ops.PackCache.invalidate()                         # the capture must contain the weight packs of the head
-        capture_stream = th.cuda.Stream(device=bb.ev.device)
-        capture_stream.wait_stream(th.cuda.current_stream())
-        th.cuda.synchronize()
-        fwd = PlanRecorder(max_lanes, pool=bb.head_pool)
-        bwd = None
         try:
-            with th.enable_grad(), th.cuda.stream(capture_stream):
-                PlanRecorder.current = fwd
-                GradBuckets.current = saved_buckets
-                fwd.begin()
-                bb.head_pool = fwd.pool
-                ops.StatArena.begin_step(bb.ev.device)
-                rows = bb.rows[:self.n_frames]
-                sel = {k: bb.x_out[k].index_select(0, rows).requires_grad_() for k in in_features}
-                _, losses = mdl.forward_detect(backbone_features={k: Fn.as_nchw(v) for k, v in sel.items()}, targets=self.labels)
-                self.losses6 = mdl.yolox_head.last_losses6
-                fwd.end()
-                bwd = PlanRecorder(max_lanes, pool=fwd.pool)
-                PlanRecorder.current = bwd
-                bwd.begin()
-                Fn.WgradSide.active = wgrad_side
-                try:
+            with step_capture(bb.ev.device, bb.head_arena, max_lanes, wgrad_side, pool=bb.head_pool) as cap:
+                with cap.forward():
+                    bb.head_pool = cap.fwd.pool
+                    rows = bb.rows[:self.n_frames]
+                    sel = {k: bb.x_out[k].index_select(0, rows).requires_grad_() for k in in_features}
+                    _, losses = mdl.forward_detect(backbone_features={k: Fn.as_nchw(v) for k, v in sel.items()}, targets=self.labels)
+                    self.losses6 = mdl.yolox_head.last_losses6
+                with cap.backward():
                     losses['loss'].backward(gradient=self.seed)
-                finally:
-                    Fn.WgradSide.active = False
-                # the gradient of the gathered rows -> the backbone plan's static slots (first B' frames; its backward adds them into the stage
-                # outputs' gradients through the static row-index buffer)
-                ops.copy_multi([bb.gsel[k][:self.n_frames] for k in in_features], [sel[k].grad for k in in_features])
-                bwd.end()
-            self.arena_high = ops.StatArena.high
-            self.fwd, self.bwd = fwd, bwd
-        except BaseException:
-            _abort_captures(capture_stream, fwd, bwd)
-            raise
+                    # the gradient of the gathered rows -> the backbone plan's static slots (first B' frames; its backward adds them into the
+                    # stage outputs' gradients through the static row-index buffer)
+                    ops.copy_multi([bb.gsel[k][:self.n_frames] for k in in_features], [sel[k].grad for k in in_features])
+                self.arena_high, self.fwd, self.bwd = cap.arena_high, cap.fwd, cap.bwd
         finally:
-            PlanRecorder.current = None
-            th.cuda.current_stream().wait_stream(capture_stream)
-            ops.StatArena.swap(*saved_arena)
-            GradBuckets.current = saved_buckets
-            Fn.WgradSide.active = saved_side
-            ops.PackCache.invalidate()                     # nothing was executed: the pack buffers do not hold what the cache believes
             self.bn_incs = [(m, m.bn_calls_pending - p0) for m, p0 in zip(mods, pending0) if m.bn_calls_pending != p0]
             for m, p0 in zip(mods, pending0):
                 m.bn_calls_pending = p0
@@ -301,19 +353,6 @@ class HeadPlan:
             if p is not None:
                 p.close()
         self.fwd = self.bwd = None
-
-
-def _abort_captures(capture_stream, *recs):
-    with th.cuda.stream(capture_stream):                  # leave no stream in capture mode behind (a capturing graph aborts in its destructor)
-        for rec in recs:
-            if rec is not None and rec.graph is not None:
-                try:
-                    Fn.WgradSide.join()
-                    rec._capture_end()
-                except Exception:                             # noqa: BLE001
-                    pass
-            if rec is not None:
-                rec.close()
 
 
 class BackbonePlan:
@@ -359,64 +398,33 @@ class BackbonePlan:
     def capture(self, module, wgrad_side: bool, max_lanes: int):
         mdl = module.mdl
         in_features = tuple(mdl.fpn.in_features)
-        saved_arena = ops.StatArena.swap(self.arena)
-        from leod_amd.parallel import GradBuckets
-        saved_buckets = GradBuckets.current
-        saved_side = Fn.WgradSide.active
-        ops.PackCache.invalidate()                         # the capture must contain the weight packs of a step
-        flat = getattr(module, '_flat', None)              # FlatParams of configure_optimizers: the recorded step starts by refreshing
-        if flat is not None:                               # its 16-bit weight shadows, and the recorded GEMMs read them
-            ops.weight_shadow_pin(True)
-        capture_stream = th.cuda.Stream(device=self.ev.device)
-        capture_stream.wait_stream(th.cuda.current_stream())
-        th.cuda.synchronize()
-        fwd = PlanRecorder(max_lanes)
-        bwd = None
-        try:
-            with th.enable_grad(), th.cuda.stream(capture_stream):
-                PlanRecorder.current = fwd
-                GradBuckets.current = saved_buckets           # boundary nodes reach the buckets through PlanRecorder.split
-                fwd.begin()
+        # FlatParams of configure_optimizers: the recorded step starts by refreshing its 16-bit weight shadows, and the recorded GEMMs read them
+        flat = getattr(module, '_flat', None)
+        refresh = None if flat is None else (lambda: flat.ensure_shadow(force=True))
+        with step_capture(self.ev.device, self.arena, max_lanes, wgrad_side) as cap:
+            try:
                 if flat is not None:
-                    flat.ensure_shadow(force=True)
-                ops.StatArena.begin_step(self.ev.device)
-                ops.rows_masked_zero(_flat(self.states), self.is_first)                       # RNNStates.reset (detection.py:95-157)
-                self.tokens = []
-                _, new_states = mdl.backbone.forward_sequence(self.ev, self.states, select_stages=in_features, inject=self)
-                ops.copy_multi(_flat(self.states), [t.detach() for t in _flat(new_states)])      # state hand-over to the next step
-                fwd.end()
+                    ops.weight_shadow_pin(True)
+                with cap.forward(first=refresh):
+                    ops.rows_masked_zero(_flat(self.states), self.is_first)                   # RNNStates.reset (detection.py:95-157)
+                    self.tokens = []
+                    _, new_states = mdl.backbone.forward_sequence(self.ev, self.states, select_stages=in_features, inject=self)
+                    ops.copy_multi(_flat(self.states), [t.detach() for t in _flat(new_states)])  # state hand-over to the next step
                 if set(self.x_out) != set(in_features):
                     raise LeodHipError('backbone plan: the stage outputs the PAFPN reads were not exposed by forward_sequence')
                 for k in in_features:                          # static gradient slots (no capture is in progress here: ordinary memory)
                     self.gsel[k] = th.zeros(self.x_out[k].shape, dtype=th.float32, device=self.ev.device)
-                bwd = PlanRecorder(max_lanes, pool=fwd.pool)
-                PlanRecorder.current = bwd
-                bwd.begin()
-                Fn.WgradSide.active = wgrad_side
-                try:
+                with cap.backward():
                     th.autograd.backward(self.tokens, [th.ones_like(t) for t in self.tokens])
-                finally:
-                    Fn.WgradSide.active = False
-                bwd.end()
-            self.tokens = []
-            self.arena_high = ops.StatArena.high
-            self.fwd, self.bwd = fwd, bwd
-            # how many kernels of the two plans read the event tensor through a re-pointable argument: the stem convolution in the forward plan and
-            # its weight gradient in the backward plan, or none (float events take the generic convolution: the batch is then copied in)
-            nf, nb = fwd.rebase_input(self.ev, self.ev), bwd.rebase_input(self.ev, self.ev)
-            self.rebase_ok, self.rebase_count = (nf >= 1 and nb >= 1), nf + nb
-        except BaseException:
-            _abort_captures(capture_stream, fwd, bwd)
-            raise
-        finally:
-            if flat is not None:
-                ops.weight_shadow_pin(False)
-            PlanRecorder.current = None
-            th.cuda.current_stream().wait_stream(capture_stream)
-            ops.StatArena.swap(*saved_arena)
-            GradBuckets.current = saved_buckets
-            Fn.WgradSide.active = saved_side
-            ops.PackCache.invalidate()                     # nothing was executed: the pack buffers do not hold what the cache believes
+                self.tokens = []
+                self.arena_high, self.fwd, self.bwd = cap.arena_high, cap.fwd, cap.bwd
+                # how many kernels of the two plans read the event tensor through a re-pointable argument: the stem convolution in the forward plan
+                # and its weight gradient in the backward plan, or none (float events take the generic convolution: the batch is then copied in)
+                nf, nb = self.fwd.rebase_input(self.ev, self.ev), self.bwd.rebase_input(self.ev, self.ev)
+                self.rebase_ok, self.rebase_count = (nf >= 1 and nb >= 1), nf + nb
+            finally:
+                if flat is not None:
+                    ops.weight_shadow_pin(False)
         return self
 
     # ---- replay -------------------------------------------------------------------------------------------------------------
@@ -472,11 +480,20 @@ class BackbonePlan:
         self.bwd.replay()
         ops.PackCache.invalidate()                         # the replayed step re-packed conv / LSTM weights behind the cache's back
 
+    def claim(self, gen: int, *needed):
+        """The one backward pass of forward number ``gen`` takes the activations, or is refused: they are gone when another forward of this
+        plan has run since, when a backward has consumed them, or when this plan or one of the ``needed`` recorders was closed."""
+        if self.uses != gen or self.consumed == gen or self.fwd is None or any(r is None for r in needed):
+            raise RuntimeError('leod_amd launch plans: backward() of a planned training step whose activations are gone (another '
+                               'training_step of the same geometry ran before this backward, backward ran twice, or the plan was evicted); '
+                               'run such steps with Module.plan_mode = False')
+        self.consumed = gen
+
     def head(self, key):
-        """-> HeadPlan | 'eager' (its capture failed before) | None"""
+        """-> HeadPlan | EAGER (its capture failed before) | None"""
         h = self.heads.get(key)
         if h is not None:
-            self.heads[key] = self.heads.pop(key)          # most recently used last
+            _to_end(self.heads, key)
         return h
 
     def add_head(self, key, h):
@@ -498,9 +515,9 @@ class BackbonePlan:
 
 
 class TrainStepPlans:
-    """Per-module cache of launch plans.  {event-tensor geometry: BackbonePlan | 'seen' | 'eager'} with a small LRU bound (each backbone
+    """Per-module cache of launch plans.  {event-tensor geometry: BackbonePlan | SEEN | EAGER} with a small LRU bound (each backbone
     plan owns the activation pool of its step: ~13 GB for RVT-S bs 8 L 21 of the 288 GB); every backbone plan holds its head plans
-    {(B', padded label width): HeadPlan} (up to LEOD_PLAN_MAX_HEADS = 64, small).  A backbone geometry is captured the second time it is
+    {(B', padded label width): HeadPlan | EAGER} (up to ``BackbonePlan.max_heads`` = 64, small).  A backbone geometry is captured the second time it is
     seen (the first, eager, step is the warm-up a capture needs); a head geometry is captured the first time it is seen under a captured
     backbone -- the labelled-frame count is data dependent and every new count would otherwise cost an eager step.  Counters:
     ``steps`` planned-path steps, ``replays`` of them executed entirely from plans captured EARLIER, ``captures`` / ``head_captures``."""
@@ -510,11 +527,7 @@ class TrainStepPlans:
         self.max_plans = 4 if max_plans is None else max_plans
         self.max_lanes = 2 if max_lanes is None else max_lanes
         self.anchor = None
-        self.captures = 0
-        self.head_captures = 0
-        self.replays = 0
-        self.steps = 0
-        self.eager_steps = 0
+        self.captures = self.head_captures = self.replays = self.steps = self.eager_steps = 0
 
     plan_dist = True        # N > 1: steps with collectives are recorded in segments (False: such steps stay eager)
 
@@ -541,85 +554,73 @@ class TrainStepPlans:
         return self.replays / n if n else 0.0
 
     def lookup(self, key):
-        """-> BackbonePlan to replay | 'capture' (second occurrence) | None (run eagerly)."""
+        """-> BackbonePlan to replay | CAPTURE (second occurrence) | None (run eagerly)."""
         e = self.entries.get(key)
         if isinstance(e, BackbonePlan):
-            self.entries[key] = self.entries.pop(key)       # most recently used last
+            _to_end(self.entries, key)
             return e
         if e is None:
-            if len(self.entries) > 64:                      # geometries seen once and never again do not accumulate; 'eager' markers
-                for k in [k for k, v in self.entries.items() if v == 'seen']:      # (failed / evicted captures) stay, bounded below
+            if len(self.entries) > 64:                      # geometries seen once and never again do not accumulate; EAGER markers
+                for k in [k for k, v in self.entries.items() if v is SEEN]:        # (failed / evicted captures) stay, bounded below
                     del self.entries[k]
-                eager = [k for k, v in self.entries.items() if v == 'eager']
+                eager = [k for k, v in self.entries.items() if v is EAGER]
                 for k in eager[:max(0, len(eager) - 256)]:
                     del self.entries[k]
-            self.entries[key] = 'seen'
+            self.entries[key] = SEEN
             return None
-        if e == 'seen':
-            return 'capture'
-        return None                                           # 'eager': a capture of this geometry failed before
+        return CAPTURE if e is SEEN else None                 # EAGER: a capture of this geometry failed before, or its plan was evicted
+
+    def _captured(self, plan, module, wgrad_side, what: str, which: str):
+        """-> ``plan`` with its step captured, or None: the capture failed, the user knows, the plan is closed."""
+        try:
+            return plan.capture(module, wgrad_side, self.max_lanes)
+        except (LeodHipError, RuntimeError) as e:
+            if os.environ.get('LEOD_PLAN_DEBUG'):
+                import traceback
+                traceback.print_exc()
+            warnings.warn(f'leod_amd: {what} could not be turned into a launch plan ({e}); {which} steps stay eager')
+            plan.close()
+            return None
 
     def build(self, key, module, ev, states_like, wgrad_side) -> Optional[BackbonePlan]:
         plans = [k for k, v in self.entries.items() if isinstance(v, BackbonePlan)]
         while len(plans) >= self.max_plans:
             old = plans.pop(0)
             self.entries.pop(old).close()
-            self.entries[old] = 'eager'                     # an evicted geometry is not captured again (no capture / evict thrash)
-        entry = BackbonePlan(key, module, ev, states_like)
-        try:
-            entry.capture(module, wgrad_side, self.max_lanes)
-        except (LeodHipError, RuntimeError) as e:
-            if os.environ.get('LEOD_PLAN_DEBUG'):
-                import traceback
-                traceback.print_exc()
-            warnings.warn(f'leod_amd: the backbone of geometry {key} could not be turned into a launch plan ({e}); its steps stay eager')
-            entry.close()
-            self.entries[key] = 'eager'
-            return None
-        self.entries[key] = entry
-        self.captures += 1
+            self.entries[old] = EAGER                       # an evicted geometry is not captured again (no capture / evict thrash)
+        entry = self._captured(BackbonePlan(key, module, ev, states_like), module, wgrad_side, f'the backbone of geometry {key}', 'its')
+        self.entries[key] = EAGER if entry is None else entry
+        self.captures += entry is not None
         return entry
 
     def build_head(self, bb: BackbonePlan, hkey, module, n_frames, nmax_pad, wgrad_side) -> Optional[HeadPlan]:
-        h = HeadPlan(bb, n_frames, nmax_pad)
-        try:
-            h.capture(module, wgrad_side, self.max_lanes)
-        except (LeodHipError, RuntimeError) as e:
-            if os.environ.get('LEOD_PLAN_DEBUG'):
-                import traceback
-                traceback.print_exc()
-            warnings.warn(f'leod_amd: the head pass for {n_frames} labelled frames could not be turned into a launch plan ({e}); such steps stay eager')
-            h.close()
-            bb.add_head(hkey, 'eager')
-            return None
-        bb.add_head(hkey, h)
-        self.head_captures += 1
+        h = self._captured(HeadPlan(bb, n_frames, nmax_pad), module, wgrad_side, f'the head pass for {n_frames} labelled frames', 'such')
+        bb.add_head(hkey, EAGER if h is None else h)
+        self.head_captures += h is not None
         return h
 
     def info(self) -> Optional[Dict[str, Any]]:
-        """What the most recently used (backbone, head) plan pair launches per step, and the cache's counters."""
+        """What the most recently used (backbone, head) plan pair launches per step, and the cache's counters.  Without a head plan:
+        planned backbone, eager head (EagerHeadGate: the N > 1 configuration)."""
         bbs = [v for v in self.entries.values() if isinstance(v, BackbonePlan)]
         if not bbs:
             return None
         bb = bbs[-1]
         hds = [h for h in bb.heads.values() if isinstance(h, HeadPlan)]
-        if not hds:
-            if bb.fwd is None or bb.bwd is None:
-                return None
-            # planned backbone, eager head (EagerHeadGate: the N > 1 configuration)
-            return {'forward': bb.fwd.info(), 'backward': bb.bwd.info(), 'backbone_forward_kernels': bb.fwd.info()['kernels'],
-                    'head_forward_kernels': None, 'head_backward_kernels': None, 'backbone_backward_kernels': bb.bwd.info()['kernels'],
-                    'head': 'eager', 'captures': self.captures, 'head_captures': 0, 'head_plans': 0, 'planned_steps': self.steps,
-                    'replays': self.replays, 'eager_steps': self.eager_steps, 'plan_hit_rate': round(self.hit_rate(), 4)}
-        hd = hds[-1]
+        if not hds and (bb.fwd is None or bb.bwd is None):
+            return None
+        bf, bw = bb.fwd.info(), bb.bwd.info()
+        hf, hw = (hds[-1].fwd.info(), hds[-1].bwd.info()) if hds else (None, None)
 
         def both(a, b):
-            return {k: (max(a[k], b[k]) if k == 'lanes' else a[k] + b[k]) for k in a}
-        return {'forward': both(bb.fwd.info(), hd.fwd.info()), 'backward': both(hd.bwd.info(), bb.bwd.info()),
-                'backbone_forward_kernels': bb.fwd.info()['kernels'], 'head_forward_kernels': hd.fwd.info()['kernels'],
-                'head_backward_kernels': hd.bwd.info()['kernels'], 'backbone_backward_kernels': bb.bwd.info()['kernels'],
-                'captures': self.captures, 'head_captures': self.head_captures, 'head_plans': len(hds), 'planned_steps': self.steps,
-                'replays': self.replays, 'eager_steps': self.eager_steps, 'plan_hit_rate': round(self.hit_rate(), 4)}
+            return a if b is None else {k: (max(a[k], b[k]) if k == 'lanes' else a[k] + b[k]) for k in a}
+        out = {'forward': both(bf, hf), 'backward': both(bw, hw), 'backbone_forward_kernels': bf['kernels'], 'head_forward_kernels': hf and hf['kernels'],
+               'head_backward_kernels': hw and hw['kernels'], 'backbone_backward_kernels': bw['kernels']}
+        if not hds:
+            out['head'] = 'eager'
+        out.update(captures=self.captures, head_captures=self.head_captures if hds else 0, head_plans=len(hds), planned_steps=self.steps,
+                   replays=self.replays, eager_steps=self.eager_steps, plan_hit_rate=round(self.hit_rate(), 4))
+        return out
 
     def clear(self):
         for v in self.entries.values():

@@ -78,3 +78,39 @@ def test_recorder_counts_its_capture_even_when_it_fails(monkeypatch):
     except RuntimeError:
         pass
     assert not rec.capturing and ops.LaunchPlan._captures_open == 0
+
+
+def test_engine_capture_tells_the_plans_about_its_capture(monkeypatch):
+    import contextlib
+    import pytest
+    import torch
+    from leod_amd import ops
+    from leod_amd.engine import TrainEngine
+    LP = ops.LaunchPlan
+    seen = []
+
+    @contextlib.contextmanager
+    def graph(g):
+        seen.append(('begin', LP._captures_open))
+        yield
+        seen.append(('end', LP._captures_open))
+    monkeypatch.setattr(torch.cuda, 'graph', graph)
+    monkeypatch.setattr(ops, 'weight_shadow_pin', lambda on: seen.append(('pin', on)))
+    eng = TrainEngine.__new__(TrainEngine)
+    eng._graph = object()
+
+    def body(fail):
+        seen.append(('body', LP._captures_open))
+        if fail:
+            raise RuntimeError('body failed')
+        return 'losses'
+    assert LP._captures_open == 0
+    eng._graph_body = lambda: body(False)
+    eng._capture_graph()
+    assert seen == [('pin', True), ('begin', 1), ('body', 1), ('end', 1), ('pin', False)] and LP._captures_open == 0
+    assert eng._g_losses == 'losses'
+    del seen[:]
+    eng._graph_body = lambda: body(True)
+    with pytest.raises(RuntimeError, match='body failed'):
+        eng._capture_graph()
+    assert seen == [('pin', True), ('begin', 1), ('body', 1), ('pin', False)] and LP._captures_open == 0
