@@ -124,6 +124,14 @@ int leod_linear_dgrad_gelu16(const float* dy, const float* kscale, const float* 
 int leod_linear_wgrad_group(int n, const void* const* dy, const int* dy_fmt, const void* const* x, const int* x_fmt,
                             const float* const* stats, const float* const* ln_w, const float* const* ln_b, float* const* dW,
                             float* const* dbias, int M, const int* N, const int* K, leod_stream_t stream);
+/* Whether leod_linear_wgrad_group launches for these n problems of M rows in the current precision mode -- a query: nothing is launched, no
+ * memory is read.  The call itself switches on the same value, so the two cannot differ.
+ *   100 + T   the LDS-DMA kernel on T x T blocks of 16 columns (104 / 106 / 108: the codes of leod_linear_wgrad_route)
+ *   -1 / -3   what the call returns for these arguments (NULL data pointers apart), its checks in their order: n outside 1 .. 4 or a NULL
+ *             array -1; then per problem, in order, an x_fmt outside 0 .. 4 -1, then -3 for precision mode f32, widths of no tile class or of
+ *             another class than the problems before, M < 8192, M not a multiple of 64, M above 60 000 (T = 6) / 400 000, a width that is
+ *             no multiple of 8; last -3 where the 16-bit copies of the fp32 operands exceed the library's 600 MiB. */
+int leod_linear_wgrad_group_route(int n, int M, const int* N, const int* K, const int* dy_fmt, const int* x_fmt);
 
 /* The whole MLP of a MaxViT block in one row-streaming launch (maxvit.py:110-118, 268-269), precision mode bf16, K = 48 / H = 192 (stage 1
  * of RVT-S / -T), M >= 16384:  z[M,K] = y + g2 * (gelu(LN(y) W1^T + b1) W2^T + b2) with the hidden in registers (csrc/k_mlp.hip).
@@ -139,6 +147,12 @@ int leod_mlp_fwd_fused(const float* y, const float* ln_w, const float* ln_b, flo
 int leod_mlp_bwd_dgrad_fused(const float* dz, const float* y, const float* stats, const float* ln_w, const float* ln_b, const float* W1,
                              const float* b1, const float* W2, const float* g2, float* dy, void* du16, float* dgamma, float* dbeta, int M,
                              int H, int K, leod_stream_t stream);
+/* Whether leod_mlp_fwd_fused (entry 0) / leod_mlp_bwd_dgrad_fused (entry 1) run for this problem in the current precision mode -- a query:
+ * nothing is launched, no memory is read.  The calls themselves switch on the same value, so the two cannot differ.
+ *   7000 + 100 (K / 16) + H / 16   the one-launch kernel: 7312 for (K, H) = (48, 192), 7416 for (64, 256), in the 16-bit precision modes
+ *                                  with M >= 16384
+ *   -3                             everything else: what the call returns (NULL pointers apart);    -1: an entry other than 0 / 1 */
+int leod_mlp_fused_route(int entry, int M, int H, int K);
 
 /* Fused ConvLSTM cell, DWSConvLSTM2d.forward with dws_conv=False (models/layers/rnn.py:37-70):
  * gates = [x|h_prev] W[4C,2C]^T + b, (f,i,o)=sigmoid, g=tanh, c=f*c_prev+i*g, h=o*tanh(c).

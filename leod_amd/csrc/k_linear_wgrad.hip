@@ -124,35 +124,51 @@ LEOD_API int leod_linear_wgrad_route(int M, int N, int K, long lddy, long ldx, l
 // issues together.  dy_fmt[k]: 0 fp32 rows, 1 bf16 rows.  x_fmt[k]: 0 fp32 rows, 1 fp32 rows through LayerNorm (stats / ln_w / ln_b of
 // problem k), 2 fp16 pre-activation through GELU, 3 bf16 rows, 4 fp16 rows.  Dense rows (strides N[k] / K[k]).
 // LEOD_ERR_UNSUPPORTED: not coverable (precision mode, row count, widths) -- nothing was launched, run the problems singly.
-LEOD_API int leod_linear_wgrad_group(int n, const void* const* dy, const int* dy_fmt, const void* const* x, const int* x_fmt,
-                                     const float* const* stats, const float* const* ln_w, const float* const* ln_b, float* const* dW,
-                                     float* const* dbias, int M, const int* N, const int* K, hipStream_t stream) {
-    if (n < 1 || n > 4 || !dy || !dy_fmt || !x || !x_fmt || !dW || !N || !K) return LEOD_ERR_ARG;
-    WgdHostProb hp[4];
+//
+// The route of the group, from the integers alone (leod_linear_wgrad_group_route): WGR_DMA + T where it launches, on T x T blocks of 16
+// columns; per problem in order LEOD_ERR_ARG for an x_fmt outside the vocabulary, then LEOD_ERR_UNSUPPORTED outside the coverage; the bound
+// of the 16-bit operand copies (kWgdOperandBytes) last.  It launches nothing and reads no device memory.
+static int wgrad_group_route(int n, int M, const int* N, const int* K, const int* dy_fmt, const int* x_fmt) {
+    if (n < 1 || n > 4 || !N || !K || !dy_fmt || !x_fmt) return LEOD_ERR_ARG;
     int T = 0;
     size_t need = 0;
     for (int k = 0; k < n; ++k) {
-        if (!dy[k] || !x[k] || !dW[k] || !xm_valid(x_fmt[k])) return LEOD_ERR_ARG;
+        if (!xm_valid(x_fmt[k])) return LEOD_ERR_ARG;
+        const int t = wgd_tile(N[k], K[k]);
+        if (leod_precision() != 1 || !t || (T && t != T) || M < 8192 || (M % kWgdRC) || M > (t == 6 ? 60000 : 400000) || (N[k] & 7) || (K[k] & 7))
+            return LEOD_ERR_UNSUPPORTED;
+        T = t;
+        need += (size_t)M * ((dy_fmt[k] ? 0 : N[k]) + (xm_is_mfma_operand(x_fmt[k]) ? 0 : K[k])) * 2;
+    }
+    return need > kWgdOperandBytes ? LEOD_ERR_UNSUPPORTED : WGR_DMA + T;
+}
+LEOD_API int leod_linear_wgrad_group_route(int n, int M, const int* N, const int* K, const int* dy_fmt, const int* x_fmt) {
+    return wgrad_group_route(n, M, N, K, dy_fmt, x_fmt);
+}
+LEOD_API int leod_linear_wgrad_group(int n, const void* const* dy, const int* dy_fmt, const void* const* x, const int* x_fmt,
+                                     const float* const* stats, const float* const* ln_w, const float* const* ln_b, float* const* dW,
+                                     float* const* dbias, int M, const int* N, const int* K, hipStream_t stream) {
+    if (!dy || !x || !dW) return LEOD_ERR_ARG;
+    const int route = wgrad_group_route(n, M, N, K, dy_fmt, x_fmt);
+    if (route < 0) return route;
+    WgdHostProb hp[4];
+    for (int k = 0; k < n; ++k) {
+        if (!dy[k] || !x[k] || !dW[k]) return LEOD_ERR_ARG;
         XRows xl{reinterpret_cast<const float*>(x[k]), (long)K[k], nullptr, nullptr, nullptr, nullptr, 0, 0};
         if (x_fmt[k] == XM_LN) {
             if (!stats || !ln_w || !ln_b || !stats[k] || !ln_w[k] || !ln_b[k]) return LEOD_ERR_ARG;
             xl.stats = stats[k]; xl.ln_w = ln_w[k]; xl.ln_b = ln_b[k];
         }
         xl.set_mode(x_fmt[k]);
-        const int t = wgd_tile(N[k], K[k]);
-        if (leod_precision() != 1 || !t || (T && t != T) || M < 8192 || (M % kWgdRC) || M > (t == 6 ? 60000 : 400000) || (N[k] & 7) || (K[k] & 7))
-            return LEOD_ERR_UNSUPPORTED;
-        T = t;
-        need += (size_t)M * ((dy_fmt[k] ? 0 : N[k]) + (xm_is_mfma_operand(x_fmt[k]) ? 0 : K[k])) * 2;
         hp[k] = WgdHostProb{dy[k], (long)N[k], xl, dW[k], (long)K[k], dbias ? dbias[k] : nullptr, N[k], K[k], dy_fmt[k] ? 1 : 0};
     }
-    if (need > kWgdOperandBytes) return LEOD_ERR_UNSUPPORTED;
     FamilyMarker fm(stream);
-    switch (T) {
+    switch (route - WGR_DMA) {
         case 6: return launch_wgrad_dma_group_t<6, 64, 3>(n, hp, M, stream);
         case 8: return launch_wgrad_dma_group_t<8, 64, 2>(n, hp, M, stream);
-        default: return launch_wgrad_dma_group_t<4, 64, 3>(n, hp, M, stream);
+        case 4: return launch_wgrad_dma_group_t<4, 64, 3>(n, hp, M, stream);
     }
+    return LEOD_ERR_ARG;
 }
 
 // 1: an attention block of this geometry may keep its attention output O and the gradient dO as bf16 rows in precision mode bf16 --

@@ -197,17 +197,31 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_fused_kernel(const float* __re
     if (tile == nfull && (M & 15)) compute(f0, tile, std::false_type{});
 }
 
+// The one routing function of the two entry points below: 7000 + 100 (K / 16) + H / 16 where the one-launch kernels run -- the 16-bit
+// precision modes, (K, H) = (48, 192) (RVT-S / -T stage 1: 7312) | (64, 256) (RVT-B stage 1: 7416), M >= 16384 -- LEOD_ERR_UNSUPPORTED
+// otherwise.  Forward and backward cover the same problems.  It launches nothing and reads no device memory.
+enum : int { MR_FUSED = 7000 };
+static int mlp_fused_route(int M, int H, int K) {
+    if (leod_precision() != 1 || !((K == 48 && H == 192) || (K == 64 && H == 256)) || M < 16384) return LEOD_ERR_UNSUPPORTED;
+    return MR_FUSED + 100 * (K / 16) + H / 16;
+}
+// entry: 0 leod_mlp_fwd_fused, 1 leod_mlp_bwd_dgrad_fused; the two switch on the same value
+LEOD_API int leod_mlp_fused_route(int entry, int M, int H, int K) {
+    return entry == 0 || entry == 1 ? mlp_fused_route(M, H, K) : LEOD_ERR_ARG;
+}
+
 // z[M,K] = y + g2 * (gelu(LN(y) W1^T + b1) W2^T + b2); u16 / stats (both or neither): the fp16 pre-activation [M,H] and the LayerNorm
-// (mean, rstd) [M,2] the backward pass reads.  Precision mode bf16, K = 48, H = 192, M >= 16384 (RVT-S / -T stage 1): anything else
-// returns LEOD_ERR_UNSUPPORTED and the caller runs leod_ln_linear_gelu16_fwd + leod_linear_lsres_gelu16_fwd.
+// (mean, rstd) [M,2] the backward pass reads.  Where mlp_fused_route refuses, the caller runs leod_ln_linear_gelu16_fwd +
+// leod_linear_lsres_gelu16_fwd.
 LEOD_API int leod_mlp_fwd_fused(const float* y, const float* ln_w, const float* ln_b, float eps, const float* W1, const float* b1,
                                 const float* W2, const float* b2, const float* g2, float* out, void* u16, float* stats, int M, int H,
                                 int K, hipStream_t stream) {
     if (!y || !ln_w || !ln_b || !W1 || !W2 || !out || ((u16 == nullptr) != (stats == nullptr))) return LEOD_ERR_ARG;
-    if (leod_precision() != 1 || !((K == 48 && H == 192) || (K == 64 && H == 256)) || M < 16384) return LEOD_ERR_UNSUPPORTED;
+    const int route = mlp_fused_route(M, H, K);
+    if (route < 0) return route;
     const int grid = min(cdiv(cdiv(M, 16), 4), 256 * 2);       // two resident workgroups per CU (1 / 4 per CU measured slower: 222 / 184 vs 181 us)
     LeodFwdScope fwd_scope;
-    if (K == 64) {                                             // RVT-B stage 1
+    if (route == MR_FUSED + 416) {                             // RVT-B stage 1
         LEOD_BY_OPFMT16({
             if (u16) hipLaunchKernelGGL((mlp_fwd_fused_kernel<4, 16, true, OF>), dim3(grid), dim3(256), 0, stream, y, ln_w, ln_b, eps, W1, b1, W2, b2, g2, out,
                                         reinterpret_cast<unsigned short*>(u16), stats, M);
@@ -430,8 +444,10 @@ LEOD_API int leod_mlp_bwd_dgrad_fused(const float* dz, const float* y, const flo
                                       const float* W1, const float* b1, const float* W2, const float* g2, float* dy, void* du16,
                                       float* dgamma, float* dbeta, int M, int H, int K, hipStream_t stream) {
     if (!dz || !y || !stats || !ln_w || !ln_b || !W1 || !W2 || !dy || !dgamma || !dbeta) return LEOD_ERR_ARG;
-    if (leod_precision() != 1 || !((K == 48 && H == 192) || (K == 64 && H == 256)) || M < 16384) return LEOD_ERR_UNSUPPORTED;
-    if (K == 64) return launch_mlp_bwd_dgrad_fused<4, 16>(dz, y, stats, ln_w, ln_b, W1, b1, W2, g2, dy, du16, dgamma, dbeta, M, stream);   // RVT-B stage 1
-    return launch_mlp_bwd_dgrad_fused<3, 12>(dz, y, stats, ln_w, ln_b, W1, b1, W2, g2, dy, du16, dgamma, dbeta, M, stream);
+    switch (const int route = mlp_fused_route(M, H, K)) {
+        case MR_FUSED + 416: return launch_mlp_bwd_dgrad_fused<4, 16>(dz, y, stats, ln_w, ln_b, W1, b1, W2, g2, dy, du16, dgamma, dbeta, M, stream);   // RVT-B stage 1
+        case MR_FUSED + 312: return launch_mlp_bwd_dgrad_fused<3, 12>(dz, y, stats, ln_w, ln_b, W1, b1, W2, g2, dy, du16, dgamma, dbeta, M, stream);
+        default: return route;
+    }
 }
 

@@ -326,68 +326,63 @@ class AttnBlockFn(Function):
         need = any(ctx.needs_input_grad)
         (n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, g1, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, g2) = params
         heads, part, window = mod.self_attn.num_heads, mod.partition_size, mod.partition_window
-        geom = (x.shape[0], x.shape[1], x.shape[2], x.shape[3], heads, part)
         # norm1: a LayerNorm with weight and bias, or the identity (the first block of a stage)
         n1 = ops.ABF_LN_AFFINE if n1w is not None and n1b is not None else (ops.ABF_NO_NORM if n1w is None and n1b is None else 0)
-        if ops.ATTN_BLOCK_FUSED and x.dim() == 4 and ops.attn_block_fwd_route(*geom, flags=n1) > 0:
+        # what this geometry launches in the current precision mode, forward and backward (ops.BlockRoutes)
+        r = ops.attn_block_routes(*x.shape, heads, part, fc1_w.shape[0], n1)
+        if ops.ATTN_BLOCK_FUSED and r.attn > 0:
             # 16-bit modes, stages 1-2: the whole attention half in one launch (csrc/k_attn_block.hip); it leaves the tensors of the
             # three launches below behind when a backward pass is to come, and none of them otherwise
             y, qkv, st1, o, lse = ops.attn_block_fwd(x, n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, g1, heads, part, window, want_saved=need)
         else:
-            # precision mode bf16: where the LDS attention kernels cover the geometry, qkv (and dqkv in backward) live in HBM as bf16
-            q16 = ops.partition_attn_16bit_ok(*geom)
-            qkv, _, st1 = ops.ln_linear_fwd(x, n1w, n1b, qkv_w, qkv_b, want_stats=need or q16, out_bf16=q16)
-            # ... and the attention output O (dO in backward) as bf16 rows where every consumer has the 16-bit path
-            o16 = q16 and ops.attn_block_o16_ok(*geom)
-            o, lse = ops.partition_attn_fwd(qkv, heads, part, window, want_lse=need, out_bf16=o16)
+            # 16-bit modes: where the LDS attention kernels cover the geometry, qkv (and dqkv in backward) live in HBM as 16-bit rows,
+            # and the attention output O (dO in backward) where every consumer has the 16-bit path
+            qkv, _, st1 = ops.ln_linear_fwd(x, n1w, n1b, qkv_w, qkv_b, want_stats=need, out_bf16=r.q16)
+            o, lse = ops.partition_attn_fwd(qkv, heads, part, window, want_lse=need, out_bf16=r.o16)
             # the pre-LayerScale outputs are NOT stored: dgamma is recovered from the un-scaled weight gradient in backward
             y, _ = ops.linear_lsres_fwd(o, proj_w, proj_b, g1, x, want_t=False, a_gelu=False)
-        # precision mode bf16, stage 1: the whole MLP in one launch, the hidden in registers (csrc/k_mlp.hip); with a backward pass to
-        # come it also leaves the fp16 pre-activation and the LayerNorm statistics behind
-        fused = ops.mlp_fwd_fused(y, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, g2, want_saved=need)
-        if fused is not None:
-            z, u, st2 = fused
-            h = None
+        if r.mlp_fwd == ops.MLP_FUSED:
+            # 16-bit modes, stage 1: the whole MLP in one launch, the hidden in registers (csrc/k_mlp.hip); with a backward pass to
+            # come it also leaves the fp16 pre-activation and the LayerNorm statistics behind
+            z, u, st2 = ops.mlp_fwd_fused(y, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, g2, want_saved=need)
+            h = u
         else:
-            # precision mode bf16, stages 1-2: u comes back as ONE fp16 tensor (h is None) and fc2 applies GELU while loading it
+            # r.u16 (16-bit modes): u comes back as ONE fp16 tensor and fc2 applies GELU while loading it; else the fp32 pair (u, gelu(u))
             u, h, st2 = ops.ln_linear_fwd(y, n2w, n2b, fc1_w, fc1_b, want_act=True, want_stats=True)
-            z, _ = ops.linear_lsres_fwd(h if h is not None else u, fc2_w, fc2_b, g2, y, want_t=False, a_gelu=h is None)
+            h = u if r.u16 else h
+            z, _ = ops.linear_lsres_fwd(h, fc2_w, fc2_b, g2, y, want_t=False, a_gelu=r.u16)
         if need:
-            ctx.mod = mod
-            ctx.u16 = h is None
-            ctx.save_for_backward(x, qkv, st1, o, lse, y, u, u if h is None else h, st2, *params)
+            ctx.mod, ctx.route = mod, r
+            ctx.save_for_backward(x, qkv, st1, o, lse, y, u, h, st2, *params)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         (x, qkv, st1, o, lse, y, u, h, st2,
          n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, g1, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, g2) = ctx.saved_tensors
-        mod = ctx.mod
+        mod, r = ctx.mod, ctx.route
         sa, mlp = mod.self_attn, mod.mlp
         heads, part, window = sa.num_heads, mod.partition_size, mod.partition_window
         dz = _cont(dz)
         # ---- dgrad chain (critical path); LayerScale is folded into the dgrad loader (dz * gamma) -------------------------
-        fused = None
-        if ctx.u16:                                           # stage 1, precision mode bf16: the MLP's dgrad chain in one launch (csrc/k_mlp.hip)
-            fused = ops.mlp_bwd_dgrad_fused(dz, y, st2, n2w, n2b, fc1_w, fc1_b, fc2_w, g2, grad_buf(mod.norm2.weight), grad_buf(mod.norm2.bias))
-        if fused is not None:
-            dy, du = fused
+        if r.mlp_bwd_fused:                                   # stage 1, 16-bit modes: the MLP's dgrad chain in one launch (csrc/k_mlp.hip)
+            dy, du = ops.mlp_bwd_dgrad_fused(dz, y, st2, n2w, n2b, fc1_w, fc1_b, fc2_w, g2, grad_buf(mod.norm2.weight), grad_buf(mod.norm2.bias))
         else:
             du = ops.linear_dgrad(dz, fc2_w, kscale=g2, aux_u=u)
             dy = ops.linear_dgrad_ln_bwd(du, fc1_w, y, st2, n2w, dz, grad_buf(mod.norm2.weight), grad_buf(mod.norm2.bias))
-        do = ops.linear_dgrad(dy, proj_w, kscale=g1, out_bf16=o.dtype is not torch.float32)
+        do = ops.linear_dgrad(dy, proj_w, kscale=g1, out_bf16=r.o16)
         dqkv = ops.partition_attn_bwd(qkv, do, lse, heads, part, window)
         # ---- weight gradients: off the critical path (side stream when the engine enables it) ------
         with _wgrad_side(dz, h, du, y, st2, dy, o, dqkv, x, st1):
             # stages 3-4 (short row ranges, LDS-DMA kernel): the four weight gradients as ONE preparation / contraction / reduce launch
-            grouped = ops.attn_block_wgrads(dz, h, ctx.u16, du, y, st2, n2w, n2b, dy, o, dqkv, x, st1, n1w, n1b,
-                                            (fc2_w, fc2_b, g2, grad_buf(mlp.net[2].weight), grad_buf(mlp.net[2].bias), grad_buf(mod.ls2.gamma)),
-                                            (grad_buf(mlp.net[0][0].weight), grad_buf(mlp.net[0][0].bias)),
-                                            (proj_w, proj_b, g1, grad_buf(sa.proj.weight), grad_buf(sa.proj.bias), grad_buf(mod.ls1.gamma)),
-                                            (grad_buf(sa.qkv.weight), grad_buf(sa.qkv.bias)))
-            if not grouped:
+            if not (r.wgrads_grouped and ops.attn_block_wgrads(
+                    dz, h, r.u16, du, y, st2, n2w, n2b, dy, o, dqkv, x, st1, n1w, n1b,
+                    (fc2_w, fc2_b, g2, grad_buf(mlp.net[2].weight), grad_buf(mlp.net[2].bias), grad_buf(mod.ls2.gamma)),
+                    (grad_buf(mlp.net[0][0].weight), grad_buf(mlp.net[0][0].bias)),
+                    (proj_w, proj_b, g1, grad_buf(sa.proj.weight), grad_buf(sa.proj.bias), grad_buf(mod.ls1.gamma)),
+                    (grad_buf(sa.qkv.weight), grad_buf(sa.qkv.bias)))):
                 ops.layerscale_linear_wgrad(dz, h, fc2_w, fc2_b, g2, grad_buf(mlp.net[2].weight), grad_buf(mlp.net[2].bias),
-                                            grad_buf(mod.ls2.gamma), h_gelu=ctx.u16)
+                                            grad_buf(mod.ls2.gamma), h_gelu=r.u16)
                 ops.linear_wgrad(du, y, grad_buf(mlp.net[0][0].weight), grad_buf(mlp.net[0][0].bias), stats=st2, ln_w=n2w, ln_b=n2b)
                 ops.layerscale_linear_wgrad(dy, o, proj_w, proj_b, g1, grad_buf(sa.proj.weight), grad_buf(sa.proj.bias),
                                             grad_buf(mod.ls1.gamma), h_gelu=False)

@@ -7,7 +7,7 @@ function raises if its input is not a contiguous fp32 CUDA(HIP) tensor or the li
 Convention: activations are channels-last.  2-D ``[M, C]`` "rows" and 4-D ``[B, H, W, C]`` maps are the
 same memory.
 """
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import ctypes
 
@@ -16,6 +16,7 @@ import torch
 from ._lib import lib, check, LeodHipError, DevPtr
 
 F32 = torch.float32
+UNSUPPORTED = -3            # what a ``*_route`` query answers where its entry point does not cover the problem (LEOD_ERR_UNSUPPORTED)
 
 
 _LIB = None
@@ -150,24 +151,22 @@ def _ln_linear_fwd(x, ln_w, ln_b, W, bias, want_act, want_stats, eps, out_bf16, 
         if ev is not None:
             _PROBE.amend('linear_gemm', 4.0 * M * K + 4.0 * N * K + out_bytes_per_el * n_out * M * N, 2.0 * M * N * K,
                          2.0 * M * K + 4.0 * N * K + 2.0 * n_out * M * N)
-    if out_bf16 and not want_act:
-        # the qkv rows in precision mode bf16 (consumed only by bf16 MFMAs): stored as bf16 where the kernels allow (rc -3: they do not)
+    if out_bf16 and not want_act and linear_route(3, M, N, K, flags=3 if ln_w is not None else 0) != UNSUPPORTED:
+        # the qkv rows in the 16-bit precision modes (consumed only by 16-bit MFMAs): stored in 16 bits where the kernels allow
         o16 = torch.empty(x.shape[:-1] + (N,), dtype=act16_dtype(), device=x.device)
         stats = _empty((M, 2), x) if ln_w is not None else None
-        rc = _l().leod_ln_linear_bf16_fwd(_p(x), _p(ln_w), _p(ln_b), eps, _p(W), _p(bias), _p(o16), _p(stats), M, N, K, _stream())
-        if rc != -3:
-            check(rc, 'ln_linear_bf16_fwd')
-            tally(2.0)
-            return o16, None, stats
-    if want_act and want_stats and ln_w is not None and is_16bit():
-        # precision mode bf16: the hidden pre-activation is stored once, as fp16 (the reference's autocast dtype); consumers apply GELU on load
+        check(_l().leod_ln_linear_bf16_fwd(_p(x), _p(ln_w), _p(ln_b), eps, _p(W), _p(bias), _p(o16), _p(stats), M, N, K, _stream()),
+              'ln_linear_bf16_fwd')
+        tally(2.0)
+        return o16, None, stats
+    if want_act and want_stats and ln_w is not None and linear_route(2, M, N, K, flags=3) != UNSUPPORTED:
+        # 16-bit precision modes: the hidden pre-activation is stored once, as fp16 (the reference's autocast dtype); consumers apply GELU on load
         u16 = torch.empty(x.shape[:-1] + (N,), dtype=torch.float16, device=x.device)
         stats = _empty((M, 2), x)
-        rc = _l().leod_ln_linear_gelu16_fwd(_p(x), _p(ln_w), _p(ln_b), eps, _p(W), _p(bias), _p(u16), _p(stats), M, N, K, _stream())
-        if rc != -3:
-            check(rc, 'ln_linear_gelu16_fwd')
-            tally(2.0)
-            return u16, None, stats
+        check(_l().leod_ln_linear_gelu16_fwd(_p(x), _p(ln_w), _p(ln_b), eps, _p(W), _p(bias), _p(u16), _p(stats), M, N, K, _stream()),
+              'ln_linear_gelu16_fwd')
+        tally(2.0)
+        return u16, None, stats
     out = _empty(x.shape[:-1] + (N,), x)
     act = _empty(out.shape, x) if want_act else None
     # always hand the kernel a statistics buffer: the LDS-staged GEMM reads precomputed (mean, rstd) from it
@@ -225,11 +224,13 @@ def _linear_lsres_fwd(a, W, bias, gamma, res, want_t, K, N, M, a_gelu=None):
 def mlp_fwd_fused(y, ln_w, ln_b, W1, b1, W2, b2, gamma, want_saved=False, eps=1e-5):
     """z = y + gamma * (gelu(LN(y) W1^T + b1) W2^T + b2) in ONE launch (csrc/k_mlp.hip) -> (z, u16 | None, stats | None), or None where
     the fused kernel does not cover the shape / precision mode (the caller then runs ln_linear_fwd + linear_lsres_fwd)."""
-    for t, n in ((y, 'y'), (ln_w, 'ln_w'), (ln_b, 'ln_b'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'), (b2, 'b2'), (gamma, 'gamma')):
-        _ck(t, name=n)
     K = y.shape[-1]
     H = W1.shape[0]
     M = y.numel() // K
+    if mlp_fused_route(0, M, H, K) == UNSUPPORTED:
+        return None
+    for t, n in ((y, 'y'), (ln_w, 'ln_w'), (ln_b, 'ln_b'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'), (b2, 'b2'), (gamma, 'gamma')):
+        _ck(t, name=n)
     out = _empty(y.shape, y)
     u16 = torch.empty(y.shape[:-1] + (H,), dtype=torch.float16, device=y.device) if want_saved else None
     stats = _empty((M, 2), y) if want_saved else None
@@ -238,8 +239,6 @@ def mlp_fwd_fused(y, ln_w, ln_b, W1, b1, W2, b2, gamma, want_saved=False, eps=1e
                                  M, H, K, _stream())
     if ev is not None:
         ev.record()
-    if rc == -3:
-        return None
     check(rc, 'mlp_fwd_fused')
     return out, u16, stats
 
@@ -247,14 +246,14 @@ def mlp_fwd_fused(y, ln_w, ln_b, W1, b1, W2, b2, gamma, want_saved=False, eps=1e
 def mlp_bwd_dgrad_fused(dz, y, stats, ln_w, ln_b, W1, b1, W2, gamma, dgamma, dbeta, want_du=True):
     """The activation-path backward of the fused MLP in ONE launch (csrc/k_mlp.hip) -> (dy, du bf16 | None), or None where it does not
     apply (the caller then runs linear_dgrad(aux_u=) + linear_dgrad_ln_bwd).  dgamma / dbeta accumulate norm2's gradients."""
-    for t, n in ((dz, 'dz'), (y, 'y'), (stats, 'stats'), (ln_w, 'ln_w'), (ln_b, 'ln_b'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'),
-                 (gamma, 'gamma'), (dgamma, 'dgamma'), (dbeta, 'dbeta')):
-        _ck(t, name=n)
     K = y.shape[-1]
     H = W1.shape[0]
     M = y.numel() // K
-    if not BF16_GRADS:
+    if not BF16_GRADS or mlp_fused_route(1, M, H, K) == UNSUPPORTED:
         return None
+    for t, n in ((dz, 'dz'), (y, 'y'), (stats, 'stats'), (ln_w, 'ln_w'), (ln_b, 'ln_b'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'),
+                 (gamma, 'gamma'), (dgamma, 'dgamma'), (dbeta, 'dbeta')):
+        _ck(t, name=n)
     dy = _empty(y.shape, y)
     du = torch.empty(y.shape[:-1] + (H,), dtype=torch.bfloat16, device=y.device) if want_du else None
     ev = _probe('linear_gemm', 12.0 * M * K + 4.0 * 2 * H * K + (2.0 * M * H if want_du else 0.0), 8.0 * M * H * K)
@@ -262,8 +261,6 @@ def mlp_bwd_dgrad_fused(dz, y, stats, ln_w, ln_b, W1, b1, W2, gamma, dgamma, dbe
                                        _p(dgamma), _p(dbeta), M, H, K, _stream())
     if ev is not None:
         ev.record()
-    if rc == -3:
-        return None
     check(rc, 'mlp_bwd_dgrad_fused')
     return dy, du
 
@@ -300,21 +297,60 @@ def partition_attn_route(entry, B, H, W, C, heads, part, flags=0) -> int:
 
 ATTN_BLOCK_FUSED = True     # the attention half of a block in one launch where attn_block_fwd_route says so; False: always the three launches
 ABF_LN_AFFINE, ABF_NO_NORM = 1, 2   # flags of ``attn_block_fwd_route`` (include/leod_hip.h): norm1 is a LayerNorm with weight and bias | the identity
-_ATTN_BLOCK_ROUTES = {}
 
 
 def attn_block_fwd_route(B, H, W, C, heads, part, flags=ABF_LN_AFFINE) -> int:
     """Whether an attention block of this geometry runs ``attn_block_fwd`` in the current precision mode: a positive route code, or the
-    negative error code that sends it to its three launches (``leod_attn_block_fwd_route`` in include/leod_hip.h; nothing is launched).
-    Remembered per precision mode: the step path asks on every block."""
-    key = (int(_l().leod_get_precision()), BF16_GRADS, B, H, W, C, heads, part[0], part[1], flags)
-    code = _ATTN_BLOCK_ROUTES.get(key)
-    if code is None:
-        if len(_ATTN_BLOCK_ROUTES) > 4096:
-            _ATTN_BLOCK_ROUTES.clear()
-        code = int(_l().leod_attn_block_fwd_route(B, H, W, C, heads, part[0], part[1], flags)) if BF16_GRADS else -3
-        _ATTN_BLOCK_ROUTES[key] = code
-    return code
+    negative error code that sends it to its three launches (``leod_attn_block_fwd_route``; nothing is launched; the step path: ``attn_block_routes``)."""
+    return int(_l().leod_attn_block_fwd_route(B, H, W, C, heads, part[0], part[1], flags)) if BF16_GRADS else UNSUPPORTED
+
+
+MLP_FUSED, MLP_PAIR16, MLP_PAIR32 = 'fused', 'pair16', 'pair32'
+
+
+class BlockRoutes(NamedTuple):
+    """What a MaxViT block of one geometry launches in one precision mode: every decision of ``functions.AttnBlockFn`` (``attn_block_routes``)."""
+    attn: int               # code of ``attn_block_fwd`` where the attention half is ONE launch (ATTN_BLOCK_FUSED is read by the caller), else <= 0:
+    q16: bool               # ... ln_linear_fwd + partition_attn_fwd + linear_lsres_fwd, qkv / dqkv rows in 16 bits
+    o16: bool               # ... and O / dO rows (a one-launch block leaves the same tensors behind)
+    mlp_fwd: str            # MLP_FUSED: mlp_fwd_fused | MLP_PAIR16: fp16 pre-activation (Linear entries 2 + 5) | MLP_PAIR32: fp32 pair (entries 0 + 1)
+    mlp_bwd_fused: bool     # mlp_bwd_dgrad_fused, else linear_dgrad + linear_dgrad_ln_bwd
+    ln2_fused: bool         # norm2's input gradient: dgrad + LayerNorm backward in one launch (Linear entry 7), else two calls
+    ln1_fused: bool         # norm1's
+    wgrads_grouped: bool    # the four weight gradients in one grouped launch (attn_block_wgrads), else singly
+
+    @property
+    def u16(self) -> bool:  # the MLP hidden is kept as ONE fp16 pre-activation; its consumers apply GELU on load
+        return self.mlp_fwd != MLP_PAIR32
+
+
+_BLOCK_ROUTES = {}
+
+
+def attn_block_routes(B, H, W, C, heads, part, hidden, norm1=ABF_LN_AFFINE) -> BlockRoutes:
+    """The routes of a block on the map [B,H,W,C] with an MLP of ``hidden`` units; norm1 as the flags of ``attn_block_fwd_route``.
+    Host state only (nothing is launched); remembered per precision mode: the step path asks on every block."""
+    mode = int(_l().leod_get_precision())
+    key = (mode, BF16_GRADS, B, H, W, C, heads, part[0], part[1], hidden, norm1)
+    r = _BLOCK_ROUTES.get(key)
+    if r is None:
+        if len(_BLOCK_ROUTES) > 4096:
+            _BLOCK_ROUTES.clear()
+        M, geom, ln1 = B * H * W, (B, H, W, C, heads, part), norm1 != ABF_NO_NORM
+        q16 = partition_attn_16bit_ok(*geom)
+        o16 = q16 and attn_block_o16_ok(*geom)
+        q16 = q16 and linear_route(3, M, 3 * C, C, flags=3 if ln1 else 0) != UNSUPPORTED
+        mlp_fwd = (MLP_FUSED if mlp_fused_route(0, M, hidden, C) > 0 else
+                   MLP_PAIR16 if linear_route(2, M, hidden, C, flags=3) != UNSUPPORTED else MLP_PAIR32)
+        u16 = mlp_fwd != MLP_PAIR32; du16 = u16 and BF16_GRADS                             # du leaves the dgrad through GELU' as bf16 rows
+        r = BlockRoutes(attn_block_fwd_route(*geom, flags=norm1), q16, o16, mlp_fwd,
+                        BF16_GRADS and mlp_fused_route(1, M, hidden, C) > 0,
+                        linear_route(7, M, hidden, C, a16=int(du16), flags=2 | 256) > 0,
+                        ln1 and linear_route(7, M, 3 * C, C, a16=int(q16), flags=2 | 256) > 0,
+                        linear_wgrad_group_route(M, (C, hidden, C, 3 * C), (hidden, C, C, C), (0, int(du16), 0, int(q16)),      # fc2, fc1, proj, qkv
+                                                 (2 if u16 else 0, 1, (4 if mode == 2 else 3) if o16 else 0, int(ln1))) > 0)     # as attn_block_wgrads
+        _BLOCK_ROUTES[key] = r
+    return r
 
 
 def attn_block_fwd(x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, gamma, heads, part, window, want_saved=False, eps=1e-5):
@@ -580,51 +616,58 @@ def linear_route(entry, M, N, K, lda=None, ldo=None, a16=0, out16=0, flags=0, ns
                                       a16, out16, flags, nsplit))
 
 
+def mlp_fused_route(entry, M, H, K) -> int:
+    """``leod_mlp_fused_route``: 7000 + 100 (K / 16) + H / 16 where ``mlp_fwd_fused`` (entry 0) / ``mlp_bwd_dgrad_fused`` (entry 1) run, else UNSUPPORTED."""
+    return int(_l().leod_mlp_fused_route(entry, M, H, K))
+
+
+def linear_wgrad_group_route(M, Ns, Ks, dy_fmts, x_fmts) -> int:
+    """``leod_linear_wgrad_group_route``: 100 + tile where ``linear_wgrad_group`` launches for these problems, else the call's negative code."""
+    return int(_l().leod_linear_wgrad_group_route(len(Ns), M, _int_array(Ns), _int_array(Ks), _int_array(dy_fmts), _int_array(x_fmts)))
+
+
 def linear_wgrad_group(problems) -> bool:
     """n <= 4 Linear weight gradients of one row count in ONE preparation / contraction / reduce launch (``leod_linear_wgrad_group``).
     problems: dicts with dy, x, dW, dbias and optionally stats + ln_w + ln_b (X = LayerNorm(x)) or gelu=True (x the fp16 pre-activation).
     False: not coverable -- nothing was launched (the caller runs them singly)."""
-    n = len(problems)
-    if not (1 <= n <= 4) or not is_16bit():
+    if not 1 <= len(problems) <= 4:
         return False
-    M = None
+    M = problems[0]['dy'].numel() // problems[0]['dW'].shape[0]
     Ns, Ks, dyf, xf = [], [], [], []
-    nb = fl = nb16 = 0.0
     for p in problems:
         dy, x, dW = p['dy'], p['x'], p['dW']
         N = dW.shape[0]
         K = dW.numel() // N
-        m = dy.numel() // N
-        if M is None:
-            M = m
-        if m != M or x.numel() != m * K or x.shape[-1] != K or p.get('x2') is not None:
-            return False
-        dy16 = dy.dtype is torch.bfloat16
-        _ck(dy, torch.bfloat16 if dy16 else F32, 'dy')
-        _ck(x, x.dtype, 'x')
         fmt = _x_fmt(x, p.get('stats'), p.get('gelu'))
-        if fmt == 2 and x.dtype is not torch.float16:
+        if dy.numel() // N != M or x.numel() != M * K or x.shape[-1] != K or p.get('x2') is not None or (fmt == 2 and x.dtype is not torch.float16):
             return False
-        for t_ in (dW, p.get('dbias'), p.get('stats'), p.get('ln_w'), p.get('ln_b')):
+        Ns.append(N); Ks.append(K); dyf.append(int(dy.dtype is torch.bfloat16)); xf.append(fmt)
+    if linear_wgrad_group_route(M, Ns, Ks, dyf, xf) == UNSUPPORTED:
+        return False
+    _linear_wgrad_group(problems, M, Ns, Ks, dyf, xf)
+    return True
+
+
+def _linear_wgrad_group(problems, M, Ns, Ks, dyf, xf):
+    """the launch of ``linear_wgrad_group``, for problems ``linear_wgrad_group_route`` covers"""
+    nb = fl = nb16 = 0.0
+    for p, N, K, dy16, fmt in zip(problems, Ns, Ks, dyf, xf):
+        _ck(p['dy'], torch.bfloat16 if dy16 else F32, 'dy')
+        _ck(p['x'], p['x'].dtype, 'x')
+        for t_ in (p['dW'], p.get('dbias'), p.get('stats'), p.get('ln_w'), p.get('ln_b')):
             _ck(t_, name='linear_wgrad_group')
-        Ns.append(N); Ks.append(K); dyf.append(1 if dy16 else 0); xf.append(fmt)
         w = _wgrad_work(M, N, K, dy16, fmt >= 2)
         nb += w[0]; fl += w[1]; nb16 += w[2]
-    if M >= 8192 and _stream() not in _WORKSPACES:
+    if _stream() not in _WORKSPACES:
         _wgrad_workspace(problems[0]['dW'].device)
     ev = _probe('linear_wgrad', nb, fl, rows=M, nbytes16=nb16)
-    rc = _l().leod_linear_wgrad_group(n, _ptr_array([p['dy'] for p in problems]), _int_array(dyf), _ptr_array([p['x'] for p in problems]), _int_array(xf),
-                                      _ptr_array([p.get('stats') for p in problems]), _ptr_array([p.get('ln_w') for p in problems]),
-                                      _ptr_array([p.get('ln_b') for p in problems]), _ptr_array([p['dW'] for p in problems]),
-                                      _ptr_array([p.get('dbias') for p in problems]), M, _int_array(Ns), _int_array(Ks), _stream())
-    if rc == -3:
-        if ev is not None:
-            _PROBE.cancel('linear_wgrad')
-        return False
-    check(rc, 'linear_wgrad_group')
+    check(_l().leod_linear_wgrad_group(len(problems), _ptr_array([p['dy'] for p in problems]), _int_array(dyf), _ptr_array([p['x'] for p in problems]),
+                                       _int_array(xf), _ptr_array([p.get('stats') for p in problems]), _ptr_array([p.get('ln_w') for p in problems]),
+                                       _ptr_array([p.get('ln_b') for p in problems]), _ptr_array([p['dW'] for p in problems]),
+                                       _ptr_array([p.get('dbias') for p in problems]), M, _int_array(Ns), _int_array(Ks), _stream()),
+          'linear_wgrad_group')
     if ev is not None:
         ev.record()
-    return True
 
 
 def attn_block_wgrads(dz, h, h_gelu, du, y, st2, n2w, n2b, dy, o, dqkv, x, st1, n1w, n1b, fc2, fc1, proj, qkv) -> bool:
@@ -633,18 +676,21 @@ def attn_block_wgrads(dz, h, h_gelu, du, y, st2, n2w, n2b, dy, o, dqkv, x, st1, 
     W2, b2, g2, dW2, db2, dg2 = fc2
     Wp, bp, g1, dWp, dbp, dg1 = proj
     (N2, K2), (Np, Kp) = W2.shape, Wp.shape
-    if not is_16bit() or dz.numel() // N2 < 8192:
+    st1 = st1 if n1w is not None else None
+    M = dz.numel() // N2
+    Ns, Ks = zip(W2.shape, fc1[0].shape, Wp.shape, qkv[0].shape)
+    dyf = [int(t.dtype is torch.bfloat16) for t in (dz, du, dy, dqkv)]
+    xf = [_x_fmt(h, None, h_gelu), 1, _x_fmt(o, None, False), _x_fmt(x, st1, False)]
+    if linear_wgrad_group_route(M, Ns, Ks, dyf, xf) == UNSUPPORTED:
         return False
     scratch = StatArena.zeros((N2 * K2 + N2 + Np * Kp + Np,), dz.device, torch.float32)
     G2, s2 = scratch[:N2 * K2].view(N2, K2), scratch[N2 * K2:N2 * K2 + N2]
     off = N2 * K2 + N2
     Gp, sp = scratch[off:off + Np * Kp].view(Np, Kp), scratch[off + Np * Kp:]
-    probs = [dict(dy=dz, x=h, dW=G2, dbias=s2, gelu=bool(h_gelu)),
-             dict(dy=du, x=y, dW=fc1[0], dbias=fc1[1], stats=st2, ln_w=n2w, ln_b=n2b),
-             dict(dy=dy, x=o, dW=Gp, dbias=sp),
-             dict(dy=dqkv, x=x, dW=qkv[0], dbias=qkv[1], stats=st1 if n1w is not None else None, ln_w=n1w, ln_b=n1b)]
-    if not linear_wgrad_group(probs):
-        return False
+    _linear_wgrad_group([dict(dy=dz, x=h, dW=G2, dbias=s2),
+                         dict(dy=du, x=y, dW=fc1[0], dbias=fc1[1], stats=st2, ln_w=n2w, ln_b=n2b),
+                         dict(dy=dy, x=o, dW=Gp, dbias=sp),
+                         dict(dy=dqkv, x=x, dW=qkv[0], dbias=qkv[1], stats=st1, ln_w=n1w, ln_b=n1b)], M, Ns, Ks, dyf, xf)
     check(_l().leod_layerscale_finalize(_p(W2), _p(b2), _p(g2), _p(G2), _p(s2), _p(dW2), _p(db2), _p(dg2), N2, K2, _stream()), 'layerscale_finalize')
     check(_l().leod_layerscale_finalize(_p(Wp), _p(bp), _p(g1), _p(Gp), _p(sp), _p(dWp), _p(dbp), _p(dg1), Np, Kp, _stream()), 'layerscale_finalize')
     return True
@@ -681,12 +727,11 @@ def linear_dgrad_ln_bwd(dy, W, x, stats, ln_w, dres, dw, db, eps=1e-5):
         _ck(t, name=n)
     N, K = W.shape
     M = dy.numel() // N
-    dx = _empty(x.shape, x)
-    rc = _l().leod_linear_dgrad_lnbwd(_p(dy), _p(W), _p(x), _p(stats), _p(ln_w), _p(dres), _p(dx), _p(dw), _p(db), M, N, K,
-                                      1 if dy16 else 0, _stream())
-    if rc == -3:                                            # shape outside the fused kernel's coverage
+    if linear_route(7, M, N, K, a16=int(dy16), flags=2 | (256 if dres is not None else 0)) == UNSUPPORTED:   # outside the fused kernel's coverage
         return layernorm_bwd(linear_dgrad(dy, W), x, stats, ln_w, dres, dw, db, eps)
-    check(rc, 'linear_dgrad_lnbwd')
+    dx = _empty(x.shape, x)
+    check(_l().leod_linear_dgrad_lnbwd(_p(dy), _p(W), _p(x), _p(stats), _p(ln_w), _p(dres), _p(dx), _p(dw), _p(db), M, N, K,
+                                       1 if dy16 else 0, _stream()), 'linear_dgrad_lnbwd')
     return dx
 
 
@@ -2329,10 +2374,6 @@ class KernelProbe:
         e0.record()
         self.events[target].append((self.step, e0, e1, nbytes, flops, nbytes if nbytes16 is None else nbytes16, rows))
         return e1
-
-    def cancel(self, target):
-        """Drops the bracket ``begin`` opened last for ``target`` (the call it was opened for launched nothing)."""
-        self.events[target].pop()
 
     def amend(self, target, nbytes, flops, nbytes16=None):
         """Sets the work of the bracket ``begin`` opened last for ``target`` (the byte count was not known when it was opened)."""
