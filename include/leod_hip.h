@@ -313,6 +313,27 @@ long leod_conv3x3_group_wgrad_workspace_floats(int B, int H, int W, int Cin, int
 int leod_conv3x3_group_wgrad(int n, const float* const* dy, const float* const* x, float* const* dw, float* const* ws, const int* B,
                              const int* H, const int* W, int Cin, int N, leod_stream_t stream);
 
+/* Grouped 1x1 / stride-1 convolutions over pixel rows: n <= 4 independent problems in ONE launch of the short-problem kernel, which has a
+ * workgroup's operands for the whole contraction in flight at once -- the single layers of the PAFPN, conv1 | conv2 of a CSP layer on one
+ * map, the three head stems.  All array arguments are HOST arrays of length n.  16-bit precision modes only.
+ * leod_conv1x1_group_route: the kernel the call `entry` (0 leod_conv1x1_group_fwd, 1 leod_conv1x1_group_dgrad) runs for members of M[k] rows,
+ * contraction length K[k] and N[k] output columns (dgrad: K = the conv's output channels, N = its input channels); flags: 2 colstats,
+ * 64 accumulate.  A query: nothing is launched.  Covered: 1 <= M <= 65536, 16 <= K <= 384, 16 <= N <= 384, K and N multiples of 16.
+ *   1 d_0 .. d_{n-1}       one launch; decimal digit d_k = row fragments per workgroup of member k (2: 32-row tiles, 4: 64-row tiles)
+ *   -1                     bad arguments (n outside 1..4, NULL, unknown entry or flag);    -3    not covered: run the members singly
+ * A group computes bit for bit what its members compute through leod_conv_nhwc_fwd / _dgrad.  Refused (-3) besides the coverage: a member
+ * whose single call is the wide-tile kernel (leod_conv_route 3000 + ..); a group whose members all have 8192 rows or more, unless it is a
+ * forward group of two or more -- such members are no faster here than alone (measured) and gain only by the launch they share.
+ * The calls switch on the same value; < 0: nothing was launched and no output was touched.
+ * forward: y_k [M][N] = x_k [M][Cin] w_k [N][Cin]^T with the BatchNorm (sum, sumsq) of y_k into colstats[k] ([stat_rep[k]][2][N] doubles,
+ * zeroed; NULL: none), as leod_conv_nhwc_fwd leaves them.  dgrad: dx_k [M][Cin] (+)= dy_k [M][N] w_k; members of one call must write
+ * different dx buffers. */
+int leod_conv1x1_group_route(int entry, int n, const int* M, const int* K, const int* N, int flags);
+int leod_conv1x1_group_fwd(int n, const float* const* x, const float* const* w, float* const* y, double* const* colstats,
+                           const int* stat_rep, const int* M, const int* Cin, const int* N, leod_stream_t stream);
+int leod_conv1x1_group_dgrad(int n, const float* const* dy, const float* const* w, float* const* dx, const int* accumulate,
+                             const int* M, const int* Cin, const int* N, leod_stream_t stream);
+
 /* Which kernel a dense-convolution call runs for this problem in the current precision mode, or the negative error it returns (NULL pointers
  * apart) -- a query: nothing is launched, no memory is read.  The calls themselves switch on the same value, so the two cannot differ.
  * entry: 0 leod_conv_nhwc_fwd, 1 leod_conv_nhwc_dgrad, 2 leod_conv_nhwc_wgrad, 3 leod_stem_conv_fwd, 4 leod_stem_conv_wgrad.  B, H, W, Cin,

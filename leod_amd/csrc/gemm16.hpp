@@ -508,6 +508,8 @@ __device__ __forceinline__ void dispatch_fast_mode(int mode, F&& f) {
     else f(std::integral_constant<int, 0>{});
 }        // prefetched global operand of a row epilogue: one 16-byte piece per row group of the lane
 
+// (conv1x1_short.hpp reproduces the sums of this epilogue bit for bit -- run()'s order and unfused squares itself, the row epilogue by calling
+// run_rows_full<6> / run_rows -- and tests/test_conv1x1_group_gpu.py compares the two for equality: a change here shows there)
 struct EpStore {
     float* out; long ld;            // primary output
     float* out2; long ld2;          // ACT_GELU_DUAL: gelu(pre) goes to out2, pre to out;  split: cols >= nsplit
@@ -868,6 +870,8 @@ struct EpLstm {                     // NT must be 4: tiles = (f, i, o, g) of cha
 //            and 4x shorter dependent MFMA chains, no atomics.
 // Operand loads run two chunks ahead of the MFMAs (register ring of depth 2).
 // =================================================================================================
+// (conv1x1_short_kernel reproduces the KS = 4 order -- chunk c into the sum of wave c & 3, then s0 + ((s1 + s2) + s3) -- for the members whose
+// single call runs here: tests/test_conv1x1_group_gpu.py::test_random_data_against_the_single_calls compares the bits)
 template <int NT, int KS, int BF, class AL, class BL, class EP>
 __global__ __launch_bounds__(256) void gemm16_kernel(AL al, BL bl, EP ep, int M, int K) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -8,6 +8,7 @@
 // Epilogues: raw store (+bias), raw store + per-channel (sum, sumsq) for training BatchNorm,
 // or folded eval-BatchNorm + SiLU.
 #include "conv_route.hpp"
+#include "conv1x1_short.hpp"
 
 static EpStore conv_epilogue(float* out, int N, const float* bias, double* colstats, int stat_rep, const float* bn_w, const float* bn_b,
                              const float* bn_rm, const float* bn_rv, float bn_eps) {
@@ -566,4 +567,52 @@ LEOD_API int leod_conv3x3_group_wgrad(int n, const float* const* dy, const float
     for (int k = 0; k < n; ++k) if (!dy[k] || !x[k] || !dw[k] || !ws[k]) return LEOD_ERR_ARG;
     if (!conv_group_routes_to(CR_WGRAD3, CE_WGRAD, CF_WS, n, H, W, Cin, N)) return LEOD_ERR_UNSUPPORTED;
     return conv3_wgrad_group_launch(n, dy, x, dw, ws, B, H, W, Cin, N, 1, stream, true);
+}
+
+// ---- grouped 1x1 / stride-1 convolutions over pixel rows: n <= 4 independent problems in one launch of conv1x1_short_kernel ----------------
+// The short GEMMs of the PAFPN and the head stems (yolo_pafpn.py:109-140, network_blocks.py:135-166, yolo_head.py:208-222): single layers,
+// conv1 | conv2 of a CSP layer on one map, the three stems.  Arrays are HOST arrays of length n.  The route query is the only place that
+// decides; the two calls switch on its code and nothing else.  < 0: nothing was launched (run the problems singly).
+LEOD_API int leod_conv1x1_group_route(int entry, int n, const int* M, const int* K, const int* N, int flags) {
+    return conv1x1_group_route(entry, n, M, K, N, flags);
+}
+// y_k [M][N] = x_k [M][Cin] w_k[N][Cin]^T, the BatchNorm (sum, sumsq) of y_k into colstats[k] ([stat_rep[k]][2][N] doubles, zeroed; NULL: none)
+LEOD_API int leod_conv1x1_group_fwd(int n, const float* const* x, const float* const* w, float* const* y, double* const* colstats,
+                                    const int* stat_rep, const int* M, const int* Cin, const int* N, hipStream_t stream) {
+    if (n < 1 || n > C1_MAX || !x || !w || !y || !colstats || !stat_rep || !M || !Cin || !N) return LEOD_ERR_ARG;
+    int flags = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!x[k] || !w[k] || !y[k] || (stat_rep[k] > 1 && (stat_rep[k] & (stat_rep[k] - 1)))) return LEOD_ERR_ARG;
+        if (colstats[k]) flags |= CF_COLSTATS;
+    }
+    LeodFwdScope fwd_scope;                                   // forward contraction: fp16 operands in precision mode 16f
+    const int route = conv1x1_group_route(C1E_FWD, n, M, Cin, N, flags);
+    if (route <= 0) return route;
+    C1Group g{};
+    g.n = n;
+    for (int k = 0; k < n; ++k) {
+        C1Prob& p = g.p[k];
+        p.a = x[k]; p.w = w[k]; p.out = y[k]; p.stats = colstats[k]; p.rep = stat_rep[k]; p.M = M[k]; p.K = Cin[k]; p.N = N[k];
+    }
+    return launch_conv1x1_group<false>(route, g, stream);
+}
+// dx_k [M][Cin] (+)= dy_k [M][N] w_k[N][Cin]; accumulate[k] != 0: dx_k += (problems of one launch must write DIFFERENT dx buffers)
+LEOD_API int leod_conv1x1_group_dgrad(int n, const float* const* dy, const float* const* w, float* const* dx, const int* accumulate,
+                                      const int* M, const int* Cin, const int* N, hipStream_t stream) {
+    if (n < 1 || n > C1_MAX || !dy || !w || !dx || !accumulate || !M || !Cin || !N) return LEOD_ERR_ARG;
+    int flags = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!dy[k] || !w[k] || !dx[k]) return LEOD_ERR_ARG;
+        for (int j = 0; j < k; ++j) if (dx[j] == dx[k]) return LEOD_ERR_ARG;
+        if (accumulate[k]) flags |= CF_ACCUMULATE;
+    }
+    const int route = conv1x1_group_route(C1E_DGRAD, n, M, N, Cin, flags);
+    if (route <= 0) return route;
+    C1Group g{};
+    g.n = n;
+    for (int k = 0; k < n; ++k) {
+        C1Prob& p = g.p[k];
+        p.a = dy[k]; p.w = w[k]; p.out = dx[k]; p.acc = accumulate[k] ? 1 : 0; p.M = M[k]; p.K = N[k]; p.N = Cin[k];
+    }
+    return launch_conv1x1_group<true>(route, g, stream);
 }

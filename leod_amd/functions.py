@@ -618,6 +618,13 @@ def _group3x3(members, maps, weights) -> bool:      # one channel geometry (the 
     return all(m.stride == 1 for m in members) and ops.conv3x3_group_ok(maps, weights)
 
 
+def _conv1x1_chunks(members, maps):
+    """Positions of the members that are dense 1x1 / stride-1 convs over ``maps`` (their inputs, or in the backward pass their output
+    gradients), in member order, in chunks of at most 4: the candidates of ``ops.conv1x1_group_fwd`` / ``_dgrad``"""
+    idx = [i for i, (m, t) in enumerate(zip(members, maps)) if m.stride == 1 and ops.is_conv1x1(m.conv_w, m.x) and t.dtype is torch.float32]
+    return [idx[j:j + 4] for j in range(0, len(idx), 4)]
+
+
 def _conv_bn_fwd(members):
     """Training forward of one or several INDEPENDENT BaseConv layers: all convs (their epilogues accumulate the column
     statistics into one contiguous block), ONE SyncBatchNorm all-reduce for the whole block, then the BN + SiLU kernels.
@@ -628,7 +635,14 @@ def _conv_bn_fwd(members):
                                [w.shape[0] for w in ws], ops.stat_replicas, xs[0].device, sync)
     zs = ops.conv3x3_group_fwd(xs, ws, stats) if _group3x3(members, xs, ws) else None
     if zs is None:
-        zs = [ops.conv_nhwc_fwd(m.x, m.conv_w, None, stride=m.stride, colstats=s) for m, s in zip(members, stats)]
+        zs = [None] * len(members)
+        for idx in _conv1x1_chunks(members, xs):                   # the short 1x1 GEMMs: one launch per <= 4 members where the route accepts
+            got = ops.conv1x1_group_fwd([xs[i] for i in idx], [ws[i] for i in idx], [stats[i] for i in idx])
+            for i, z in zip(idx, got or ()):
+                zs[i] = z
+        for i, (m, s) in enumerate(zip(members, stats)):
+            if zs[i] is None:
+                zs[i] = ops.conv_nhwc_fwd(m.x, m.conv_w, None, stride=m.stride, colstats=s)
     images = _SYNC_BN['images'] if sync else None
     if sync:
         assert images is not None, 'SyncBatchNorm: functions.sync_bn_begin(n_images) must open the pass (YoloXDetector.forward_detect does)'
@@ -694,8 +708,12 @@ def _conv_bn_bwd(members):
         if len(idx) > 1 and _group3x3(ms, dz_r, [m.conv_w.transpose(0, 1) for m in ms]):
             done = ops.conv3x3_group_dgrad(dz_r, [m.conv_w for m in ms], [m.x.shape for m in ms], outs, [rnd > 0] * len(idx))
         if not done:
-            for m, dz, out in zip(ms, dz_r, outs):
-                ops.conv_nhwc_dgrad(dz, m.conv_w, m.x.shape, stride=m.stride, out=out, accumulate=rnd > 0)
+            single = set(range(len(idx)))
+            for js in _conv1x1_chunks(ms, dz_r):                   # (the group launches of a round go first: its members write different buffers)
+                if ops.conv1x1_group_dgrad([dz_r[j] for j in js], [ms[j].conv_w for j in js], [outs[j] for j in js], [rnd > 0] * len(js)):
+                    single -= set(js)
+            for j in sorted(single):
+                ops.conv_nhwc_dgrad(dz_r[j], ms[j].conv_w, ms[j].x.shape, stride=ms[j].stride, out=outs[j], accumulate=rnd > 0)
     WgradSide.hold_main = prev_hold
     return dxs
 

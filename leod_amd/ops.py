@@ -1037,6 +1037,64 @@ def conv3x3_group_wgrad(dys, xs, dws) -> bool:
     return True
 
 
+_CONV1X1_ROUTES = {}
+
+
+def conv1x1_group_route(entry, shapes, flags=0) -> int:
+    """``leod_conv1x1_group_route`` for members of (rows, contraction length, output columns) -- entry 0: (M, Cin, N) of the forward call,
+    1: (M, N, Cin) of the dgrad -- in the current precision mode: the route code of the one launch, or the negative code of a refusal.
+    Nothing is launched; answers are remembered per precision mode like those of ``conv_route``."""
+    key = (int(_l().leod_get_precision()), entry, tuple(tuple(int(d) for d in sh) for sh in shapes), flags)
+    code = _CONV1X1_ROUTES.get(key)
+    if code is None:
+        if len(_CONV1X1_ROUTES) > 4096:
+            _CONV1X1_ROUTES.clear()
+        dims = [_int_array([sh[d] for sh in key[2]]) for d in range(3)]
+        code = _CONV1X1_ROUTES[key] = int(_l().leod_conv1x1_group_route(entry, len(key[2]), *dims, flags))
+    return code
+
+
+def is_conv1x1(w, x) -> bool:
+    """a dense 1x1 conv weight [N,Cin,1,1] over an fp32 NHWC device map of Cin channels: its stride-1 form is a GEMM over the pixel rows"""
+    return (w.dim() == 4 and w.shape[-1] == 1 and w.shape[-2] == 1 and x.dim() == 4 and w.shape[1] == x.shape[-1] and x.dtype is F32
+            and x.is_cuda)
+
+
+def conv1x1_group_ok(entry, shapes) -> bool:
+    """1..4 stride-1 1x1 convs (``conv1x1_group_route``'s members) go out as ONE launch of the short-problem kernel: the one question
+    ``conv1x1_group_fwd`` / ``_dgrad`` ask before they allocate or launch anything"""
+    return conv1x1_group_route(entry, shapes) > 0
+
+
+def conv1x1_group_fwd(xs, ws, colstats):
+    """[x_k [B,H,W,Cin]], [w_k [N,Cin,1,1]], [colstats_k: zero-filled float64 [R,2,N] | None] -> [y_k [B,H,W,N]] in ONE launch, or None where
+    the route refuses the group (nothing was allocated or launched: run them singly)."""
+    for t in (*xs, *ws):
+        _ck(t, name='conv1x1_group')
+    for c in colstats:
+        _ck(c, torch.float64, 'colstats')
+    shapes = [(x.numel() // x.shape[-1], x.shape[-1], w.shape[0]) for x, w in zip(xs, ws)]
+    if not (1 <= len(xs) <= 4) or not conv1x1_group_ok(0, shapes):
+        return None
+    ys = [_empty(tuple(x.shape[:-1]) + (w.shape[0],), x) for x, w in zip(xs, ws)]
+    check(_l().leod_conv1x1_group_fwd(len(xs), _ptr_array(xs), _ptr_array(ws), _ptr_array(ys), _ptr_array(colstats),
+                                       _int_array([1 if c is None else _replicas(c) for c in colstats]),
+                                       *[_int_array([sh[d] for sh in shapes]) for d in range(3)], _stream()), 'conv1x1_group_fwd')
+    return ys
+
+
+def conv1x1_group_dgrad(dys, ws, outs, accumulate) -> bool:
+    """outs[k] [B,H,W,Cin] (+)= dys[k] [B,H,W,N] w_k [N,Cin,1,1] in ONE launch; False where the route refuses (nothing was written)."""
+    for t in (*dys, *ws, *outs):
+        _ck(t, name='conv1x1_group')
+    shapes = [(dy.numel() // dy.shape[-1], w.shape[1], w.shape[0]) for dy, w in zip(dys, ws)]         # (M, Cin, N)
+    if not (1 <= len(dys) <= 4) or not conv1x1_group_ok(1, [(m, n, c) for m, c, n in shapes]):
+        return False
+    check(_l().leod_conv1x1_group_dgrad(len(dys), _ptr_array(dys), _ptr_array(ws), _ptr_array(outs), _int_array([1 if a else 0 for a in accumulate]),
+                                         *[_int_array([sh[d] for sh in shapes]) for d in range(3)], _stream()), 'conv1x1_group_dgrad')
+    return True
+
+
 def conv_nhwc_wgrad(dy, x, dw, dbias=None, stride=1):
     for t, n in ((dy, 'dy'), (x, 'x'), (dw, 'dw'), (dbias, 'dbias')):
         _ck(t, name=n)
