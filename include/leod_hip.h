@@ -732,6 +732,25 @@ int leod_render_frames_u8(const void* ev, int ev_is_f32, unsigned char* out, int
  * leftmost of the 5 columns. */
 int leod_render_font(unsigned char* dst);
 
+/* Baseline JPEG of such frames (csrc/k_jpeg.hip; the reference hands its frames to an mp4 writer on the host, vis_pred.py:216-227): rgb
+ * [n,H,W,3] uint8 -> n complete JFIF files back to back.  The stream is fixed: 4:4:4, the Annex K.1 quantisation
+ * tables under the IJG rule for quality 1 .. 100, the Annex K.3 Huffman tables, one restart interval per row of 8 x 8 blocks, partial
+ * blocks repeating the last column / row; colour conversion, DCT and quantisation in integers.  Two calls with the sizes between them:
+ * leod_jpeg_scan transforms and codes the frames into ws and writes offsets[0 .. n] = base + the first byte of every file, offsets[n] = base +
+ * all of them (device int64; the caller reads offsets[n] back, checks its buffer, and calls)
+ * leod_jpeg_emit with the same n, H, W, quality, base and the untouched ws: it writes the files to out[0 .. offsets[n] - base) -- out is
+ * where byte `base` of the blob goes, out_bytes the room from there; no byte at or behind out + out_bytes is written whatever ws holds.
+ * leod_jpeg_query (host only): *ws_bytes = workspace of n frames (16-byte aligned; no more than n times that of one frame), *out_bound =
+ * the most n files can take (header + 432 bytes per block and component + 2 per row), *header_bytes = bytes in front of a file's scan.
+ * Outputs may be NULL.
+ * Return 0; -1 for NULL pointers, n / H / W < 1, H or W above 65535, quality outside 1 .. 100, base < 0, a ws that is too small or not
+ * 16-byte aligned; -2 if a launch failed. */
+int leod_jpeg_query(int n, int H, int W, long* ws_bytes, long* out_bound, int* header_bytes);
+int leod_jpeg_scan(const unsigned char* rgb, int n, int H, int W, int quality, void* ws, long ws_bytes, long* offsets, long base,
+                   leod_stream_t stream);
+int leod_jpeg_emit(const void* ws, long ws_bytes, int n, int H, int W, int quality, unsigned char* out, long out_bytes,
+                   long base, leod_stream_t stream);
+
 /* dgrad of a Linear fused with the LayerNorm backward of its producer (x -> norm -> Linear, maxvit.py:267-269,110-118):
  * dx[M,K] = LN-backward(dy[M,N] @ W[N,K]) (+ dres), dgamma[K] += sum dn*xhat, dbeta[K] += sum dn, with x[M,K] the LayerNorm
  * input and stats[M,2] its saved (mean, rstd).  Stage-1 shapes only (K = 48, N = 144 / 192, M >= 16384): returns -3

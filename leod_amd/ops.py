@@ -2295,6 +2295,68 @@ def render_frames(ev, frame_off=None, items=None, text=None, upsample=2, out=Non
 
 
 # ---------------------------------------------------------------------------------------------------
+# baseline JPEG of rendered frames (csrc/k_jpeg.hip)
+# ---------------------------------------------------------------------------------------------------
+JPEG_WS_BYTES = 16 << 20                                     # default workspace bound of encode_jpeg, as in the ingestion ops
+
+
+def jpeg_query(n: int, height: int, width: int):
+    """(workspace bytes for ``n`` frames of height x width, the most bytes their files can take, bytes of a file's header): the
+    encoder's own constants (csrc/k_jpeg.hip)."""
+    ws, bound, hdr = (ctypes.c_long * 1)(), (ctypes.c_long * 1)(), (ctypes.c_int * 1)()
+    check(_l().leod_jpeg_query(int(n), int(height), int(width), ws, bound, hdr), 'jpeg_query')
+    return int(ws[0]), int(bound[0]), int(hdr[0])
+
+
+def encode_jpeg(frames, quality=90, out=None, ws_bytes=None):
+    """RGB frames uint8 [N, H, W, 3] on the device (what ``render_frames`` returns; H, W up to 65535) -> (blob, offsets): N complete
+    baseline JFIF files back to back in one device uint8 buffer, and int64 [N + 1] on the device with file i at
+    blob[offsets[i]:offsets[i + 1]].  The stream is fixed: 4:4:4, IJG tables of ``quality`` 1 .. 100, the standard's
+    example Huffman tables, one restart interval per row of blocks.  ``out``: a contiguous device uint8 buffer to store the files in;
+    its first offsets[N] bytes are returned as the blob, nothing behind them is written, and a buffer that does not hold them all raises
+    ``LeodHipError`` (nothing behind ITS end is written either).  ``ws_bytes`` (None: ``JPEG_WS_BYTES``) bounds the workspace: frames that
+    need more are encoded in sub-chunks, each with one read-back (its byte count)."""
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise LeodHipError(f'encode_jpeg: quality must be an integer in 1 .. 100, got {quality!r}')
+    quality = int(quality)
+    _ck(frames, torch.uint8, 'frames')
+    if frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) < 1 or max(frames.shape[1:3]) > 65535:
+        raise LeodHipError(f'encode_jpeg: frames must be [N, H, W, 3] with N, H, W >= 1 and H, W <= 65535, got {tuple(frames.shape)}')
+    N, H, W = (int(s) for s in frames.shape[:3])
+    dev = frames.device
+    if out is not None:
+        _ck(out, torch.uint8, 'out')
+        out = out.reshape(-1)
+    per_frame = jpeg_query(1, H, W)[0]
+    ws_bytes = JPEG_WS_BYTES if ws_bytes is None else int(ws_bytes)
+    if ws_bytes < per_frame:
+        raise LeodHipError(f'ws_bytes={ws_bytes}: at least {per_frame} (one frame of {H} x {W}) expected')
+    step = min(N, ws_bytes // per_frame)
+    ws_need = jpeg_query(step, H, W)[0]
+    ws = torch.empty((ws_need // 8,), dtype=torch.int64, device=dev)
+    offsets = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+    pieces, base = [], 0
+    for f0 in range(0, N, step):
+        n = min(step, N - f0)
+        check(_l().leod_jpeg_scan(_p(frames[f0:f0 + n]), n, H, W, quality, _p(ws), ws_need, _p(offsets[f0:]), base, _stream()),
+              'encode_jpeg (scan)')
+        end = int(offsets[f0 + n].item())
+        if out is None:
+            piece = torch.empty((end - base,), dtype=torch.uint8, device=dev)
+            pieces.append(piece)
+            room = piece
+        else:
+            if end > out.numel():
+                raise LeodHipError(f'out: {out.numel()} bytes do not hold the {end} bytes of the first {f0 + n} files')
+            room = out[base:]
+        check(_l().leod_jpeg_emit(_p(ws), ws_need, n, H, W, quality, _p(room), room.numel(), base, _stream()), 'encode_jpeg (emit)')
+        base = end
+    if out is not None:
+        return out[:base], offsets
+    return (pieces[0] if len(pieces) == 1 else torch.cat(pieces)), offsets
+
+
+# ---------------------------------------------------------------------------------------------------
 # launch plans: a captured hipGraph replayed as plain stream launches (csrc/k_plan.hip)
 # ---------------------------------------------------------------------------------------------------
 class LaunchPlan:

@@ -5,11 +5,14 @@ pseudo-label filter would drop, the ground truth and a timestamp drawn over the 
     run_visualization(config, module, fetch_data_module(config), 'vis', num_video=5)
 
     python -m leod_amd.visualize --dataset gen1 --size small --path DATA --checkpoint CKPT --out vis [--num-video 5] [--reverse]
+                                 [--video png|avi] [--jpeg-quality 90]
 
 The frames are rendered on the device in one pass (``ops.render_frames``: event image, box outlines and text in the library's own 5 x 7
-font) and written as numbered 8-bit RGB PNG files with the standard library; turning ``%05d.png`` + ``frames.json`` (fps) into an mp4 is
-left to whatever encoder is at hand.  OpenCV's thick-line and Hershey-font rasterisers are not reproduced: the raster rules of
-``leod_render_frames_u8`` are the specification."""
+font).  ``--video png`` (the default) writes them as numbered 8-bit RGB PNG files with the standard library, ``%05d.png`` + ``frames.json``
+(fps).  ``--video avi`` writes a video file: the frames stay on the device, ``ops.encode_jpeg`` makes a baseline JPEG file of each, and
+one copy per ``RENDER_CHUNK`` frames brings them to the host, where ``utils.mjpeg.AviWriter`` puts them into a Motion-JPEG AVI.  OpenCV's
+thick-line and Hershey-font rasterisers are not reproduced: the raster rules of ``leod_render_frames_u8`` are the specification, and
+so are the stream rules of the JPEG files."""
 import argparse
 import contextlib
 import copy
@@ -17,7 +20,7 @@ import json
 import os
 import struct
 import zlib
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -26,6 +29,7 @@ from leod_amd import ops
 from leod_amd.data.utils.types import DataType
 from leod_amd.modules.utils.detection import DATA_KEY
 from leod_amd.modules.utils.ssod import filter_pred_boxes
+from leod_amd.utils.mjpeg import AviWriter
 
 UPSAMPLE = 2
 SKIP = 2
@@ -34,6 +38,7 @@ FRAME_DT = 0.05                      # seconds between two event frames (the 50 
 RENDER_CHUNK = 128                   # frames per ops.render_frames call and per device -> host copy
 GREEN, RED, BLACK = (0, 255, 0), (255, 0, 0), (0, 0, 0)
 GAP = 5                              # black pixels between the forward and the time-reversed frame
+VIDEO_MODES = ('png', 'avi')
 
 
 def _rgb(c: Tuple[int, int, int]) -> int:
@@ -116,10 +121,28 @@ def build_items(preds_keep, preds_remove, labels, label_map, times, upsample: in
             np.frombuffer(bytes(text), dtype=np.uint8).copy())
 
 
-def render_sequence(preds, ev_seq: torch.Tensor, labels, filter_fn: Callable, label_map, prev_t: float = 0.):
+class EncodedVideo(NamedTuple):
+    """Video frames as JPEG files: ``jpeg[k]`` is frame k (a frame the video holds several times is the same bytes object every time),
+    ``hw`` the frame size, ``pixels`` uint8 [T, H', W', 3] on the host, or None where nobody asked for them."""
+    jpeg: List[bytes]
+    hw: Tuple[int, int]
+    pixels: Optional[np.ndarray]
+
+
+def encode_frames(frames: torch.Tensor, quality: int) -> List[bytes]:
+    """uint8 [n, H, W, 3] on the device -> n JPEG files: ``ops.encode_jpeg`` and one device -> host copy of the blob (and one of its offsets)."""
+    blob, off = ops.encode_jpeg(frames, quality)
+    data, off = memoryview(blob.cpu().numpy()), off.cpu().tolist()
+    return [bytes(data[off[i]:off[i + 1]]) for i in range(frames.shape[0])]
+
+
+def render_sequence(preds, ev_seq: torch.Tensor, labels, filter_fn: Callable, label_map, prev_t: float = 0.,
+                    jpeg_quality: Optional[int] = None, pixels: bool = False):
     """One ``predict_one_seq`` result -> (video frames uint8 [T, H', W', 3] on the host, time of the frame after the last).  Frame i
     carries the time prev_t + i * 0.05 s; which frames the video shows, and how often, is ``video_frame_indices``.  Every distinct frame
-    is rendered once: one ``ops.render_frames`` call and one device -> host copy per ``RENDER_CHUNK`` frames."""
+    is rendered once: one ``ops.render_frames`` call and one device -> host copy per ``RENDER_CHUNK`` frames.
+    With ``jpeg_quality`` the frames stay on the device and are encoded there, once each: -> (``EncodedVideo``, time), the pixels in it
+    only with ``pixels`` (a second copy per chunk)."""
     L = ev_seq.shape[0]
     assert len(preds) == len(labels) == L
     shown = video_frame_indices([l is not None for l in labels], len(label_map))
@@ -129,7 +152,10 @@ def render_sequence(preds, ev_seq: torch.Tensor, labels, filter_fn: Callable, la
     flat = torch.cat([p.reshape(-1, 7).float() for p in preds if p is not None and len(p)]).cpu() if sum(counts) else torch.zeros((0, 7))
     starts = np.concatenate([[0], np.cumsum(counts)])
     up = UPSAMPLE
-    out = np.empty((len(distinct), up * ev_seq.shape[2], up * ev_seq.shape[3], 3), dtype=np.uint8)
+    hw = (up * ev_seq.shape[2], up * ev_seq.shape[3])
+    want_pixels = jpeg_quality is None or pixels
+    out = np.empty((len(distinct) if want_pixels else 0,) + hw + (3,), dtype=np.uint8)
+    files: List[bytes] = []
     for lo in range(0, len(distinct), RENDER_CHUNK):
         idx = distinct[lo:lo + RENDER_CHUNK]
         keep, remove = [], []
@@ -142,9 +168,15 @@ def render_sequence(preds, ev_seq: torch.Tensor, labels, filter_fn: Callable, la
         ev = ev_seq[idx[0]:idx[-1] + 1] if contiguous else ev_seq[torch.as_tensor(idx, device=ev_seq.device)]
         if ev.dtype not in (torch.uint8, torch.float32):
             ev = ev.float()
-        out[lo:lo + len(idx)] = ops.render_frames(ev.contiguous(), frame_off, items, text, upsample=up).cpu().numpy()
+        frames = ops.render_frames(ev.contiguous(), frame_off, items, text, upsample=up)
+        if jpeg_quality is not None:
+            files.extend(encode_frames(frames, jpeg_quality))
+        if want_pixels:
+            out[lo:lo + len(idx)] = frames.cpu().numpy()
     pos = {i: n for n, i in enumerate(distinct)}
-    video = out[[pos[i] for i in shown]] if shown else out[:0]
+    video = (out[[pos[i] for i in shown]] if shown else out[:0]) if want_pixels else None
+    if jpeg_quality is not None:
+        video = EncodedVideo([files[pos[i]] for i in shown], hw, video if pixels else None)
     return video, prev_t + L * FRAME_DT
 
 
@@ -213,9 +245,30 @@ def _write_frames(directory: str, frames: np.ndarray, source: List[int], times: 
                                           for k, (s, t) in enumerate(zip(source, times))]}, f)
 
 
-def _one_pass(config, module, data_module, label_map, filter_fn, num_video: int, device, on_recording: Callable) -> int:
-    """Streams the test split one recording at a time through ``predict_one_seq`` + ``render_sequence``; ``on_recording(name, frames,
-    source frame indices, times)`` for every finished recording but the first of Gen1 (vis_pred.py:264-281).  -> recordings handed over."""
+def _write_video(stem: str, jpeg: Sequence[bytes], hw: Tuple[int, int], source: List[int], times: List[float]) -> None:
+    """``stem``.avi (Motion-JPEG; ``stem``_001.avi ... where one file would pass 1 GiB) and ``stem``.frames.json: what ``_write_frames`` says
+    about a directory of PNG files, with ``frame`` = index in the video in the place of ``file``, and the names of the video files."""
+    os.makedirs(os.path.dirname(stem) or '.', exist_ok=True)
+    with AviWriter(stem + '.avi', hw[1], hw[0], FPS) as avi:
+        for data in jpeg:
+            avi.append(data)
+    with open(stem + '.frames.json', 'w') as f:
+        json.dump({'fps': FPS, 'video': [os.path.basename(p) for p in avi.paths],
+                   'frames': [{'frame': k, 'source_frame': int(s), 't': round(float(t), 6)} for k, (s, t) in enumerate(zip(source, times))]}, f)
+
+
+def _join(parts):
+    """The per-sample results of ``render_sequence`` of one recording as one."""
+    if isinstance(parts[0], EncodedVideo):
+        px = None if parts[0].pixels is None else np.concatenate([p.pixels for p in parts])
+        return EncodedVideo([f for p in parts for f in p.jpeg], parts[0].hw, px)
+    return np.concatenate(parts)
+
+
+def _one_pass(config, module, data_module, label_map, filter_fn, num_video: int, device, on_recording: Callable, **render_kw) -> int:
+    """Streams the test split one recording at a time through ``predict_one_seq`` + ``render_sequence`` (``render_kw``: its JPEG options);
+    ``on_recording(name, frames, source frame indices, times)`` for every finished recording but the first of Gen1 (vis_pred.py:264-281).
+    -> recordings handed over."""
     from leod_amd.train import _device_batches
     is_gen1 = config.dataset.name == 'gen1'
     data_module.setup('test')
@@ -232,7 +285,7 @@ def _one_pass(config, module, data_module, label_map, filter_fn, num_video: int,
             batch = _truncate_padding(batch)
             if len(batch[DATA_KEY][DataType.EV_REPR]):
                 preds, ev_seq, labels = module.predict_one_seq(batch)
-                video, next_t = render_sequence(preds, ev_seq, labels, filter_fn, label_map, prev_t=prev_t)
+                video, next_t = render_sequence(preds, ev_seq, labels, filter_fn, label_map, prev_t=prev_t, **render_kw)
                 shown = video_frame_indices([l is not None for l in labels], len(label_map))
                 parts.append(video)
                 ev_idx = batch[DATA_KEY].get(DataType.EV_IDX)   # the frames' positions in the recording (a stream may start after frame 0)
@@ -242,7 +295,7 @@ def _one_pass(config, module, data_module, label_map, filter_fn, num_video: int,
                 prev_t, frame0 = next_t, frame0 + len(labels)
             if eoe:
                 if parts:
-                    on_recording(name, np.concatenate(parts), source, times)
+                    on_recording(name, _join(parts), source, times)
                     done += 1
                 parts, source, times, video_cnt, prev_t, frame0 = [], [], [], video_cnt + 1, 0., 0
             if done >= num_video:
@@ -251,7 +304,7 @@ def _one_pass(config, module, data_module, label_map, filter_fn, num_video: int,
 
 
 def run_visualization(config, module, data_module, out_dir: str, num_video: Optional[int] = None, reverse: Optional[bool] = None,
-                      sequence_length: Optional[int] = None):
+                      sequence_length: Optional[int] = None, video: Optional[str] = None, jpeg_quality: int = 90):
     """The loop of vis_pred.py:229-319.  One recording at a time (batch size 1, one loader worker, samples of 640 frames for Gen1 and
     256 for Gen4 unless ``sequence_length`` says otherwise), ``num_video`` recordings of the test split (``dataset.test_ratio`` = num_video /
     400 for Gen1, / 100 for Gen4; every recording when that would select none), the first Gen1 recording skipped.  Writes
@@ -260,7 +313,15 @@ def run_visualization(config, module, data_module, out_dir: str, num_video: Opti
     the common length) under ``<recording>_both/``; the forward frames stay where they are (the reference deletes its forward file).
     ``num_video`` counts the recordings written, not the skipped one.  Like the script, the call CHANGES ``config`` (dataset.sequence_length,
     dataset.test_ratio, batch_size.eval, hardware.num_workers.eval) and ``data_module`` (dataset_config, eval batch size and workers) in
-    place.  -> {'dir', 'recordings': [names], 'both': [names]}."""
+    place.  -> {'dir', 'recordings': [names], 'both': [names]}.
+    ``video`` = 'avi' (None: ``config.video``, else 'png'): ``out_dir/<exp_name>/<recording>.avi`` and ``<recording>.frames.json`` = {fps, video:
+    [file names], frames: [{frame, source_frame, t}]} instead of the directory of PNG files, JPEG frames of ``jpeg_quality`` encoded on the
+    device; with ``reverse`` also ``<recording>_both.avi``: the composite is built on the host as above, from the pixels of the forward
+    pass, which this mode keeps in host memory until the second pass has used them, and goes to the device to be encoded."""
+    video = str(config.get('video', 'png') if video is None else video)
+    if video not in VIDEO_MODES:
+        raise ValueError(f'video={video!r}: one of {VIDEO_MODES} expected')
+    avi = video == 'avi'
     from leod_amd.utils.evaluation.prophesee.evaluator import get_labelmap
     num_video = int(config.get('num_video', 5) if num_video is None else num_video)
     reverse = bool(config.get('reverse', False) if reverse is None else reverse)
@@ -284,10 +345,18 @@ def run_visualization(config, module, data_module, out_dir: str, num_video: Opti
     os.makedirs(vis_dir, exist_ok=True)
     summary = {'dir': vis_dir, 'recordings': [], 'both': []}
 
+    kept = {}                                                    # avi + reverse: recording -> (forward pixels, source frames, times)
+
     def forward(name, frames, source, times):
-        _write_frames(os.path.join(vis_dir, name), frames, source, times)
+        if avi:
+            _write_video(os.path.join(vis_dir, name), frames.jpeg, frames.hw, source, times)
+            if reverse:
+                kept[name] = (frames.pixels, list(source), [round(float(t), 6) for t in times])
+        else:
+            _write_frames(os.path.join(vis_dir, name), frames, source, times)
         summary['recordings'].append(name)
-    _one_pass(config, module, data_module, label_map, filter_fn, num_video, device, forward)
+    render_kw = dict(jpeg_quality=int(jpeg_quality), pixels=reverse) if avi else {}
+    _one_pass(config, module, data_module, label_map, filter_fn, num_video, device, forward, **render_kw)
     if not reverse:
         return summary
     rev_module = copy.copy(data_module)                          # the same loaders over the recordings read backwards (vis_pred.py:285-290)
@@ -296,17 +365,28 @@ def run_visualization(config, module, data_module, out_dir: str, num_video: Opti
 
     def both(name, frames, source, times):
         fwd_dir = os.path.join(vis_dir, name)
-        meta = json.load(open(os.path.join(fwd_dir, 'frames.json')))['frames']
+        if avi:
+            fwd_pixels, fwd_source, fwd_t = kept.pop(name)
+            meta = [{'source_frame': s, 't': t} for s, t in zip(fwd_source, fwd_t)]
+        else:
+            meta = json.load(open(os.path.join(fwd_dir, 'frames.json')))['frames']
         frames = frames[::-1]                                    # back into forward time
         n = min(len(meta), len(frames))
         rows = []
         for k in range(n):
-            a, b = read_png(os.path.join(fwd_dir, meta[k]['file'])), frames[k]
+            a, b = fwd_pixels[k] if avi else read_png(os.path.join(fwd_dir, meta[k]['file'])), frames[k]
             h, w = min(a.shape[0], b.shape[0]), min(a.shape[1], b.shape[1])
             row = np.zeros((h, 2 * w + GAP, 3), dtype=np.uint8)
             row[:, :w], row[:, w + GAP:] = a[:h, :w], b[:h, :w]
             rows.append(row)
-        _write_frames(os.path.join(vis_dir, name + '_both'), rows, [m['source_frame'] for m in meta[:n]], [m['t'] for m in meta[:n]])
+        if avi:
+            jpeg = []
+            for lo in range(0, n, RENDER_CHUNK):
+                jpeg.extend(encode_frames(torch.from_numpy(np.stack(rows[lo:lo + RENDER_CHUNK])).to(device), int(jpeg_quality)))
+            hw = rows[0].shape[:2] if rows else (1, 1)
+            _write_video(os.path.join(vis_dir, name + '_both'), jpeg, hw, [m['source_frame'] for m in meta[:n]], [m['t'] for m in meta[:n]])
+        else:
+            _write_frames(os.path.join(vis_dir, name + '_both'), rows, [m['source_frame'] for m in meta[:n]], [m['t'] for m in meta[:n]])
         summary['both'].append(name)
     _one_pass(config, module, rev_module, label_map, filter_fn, num_video, device, both)
     return summary
@@ -323,13 +403,15 @@ def main(argv=None) -> int:
     ap.add_argument('--out', default='vis')
     ap.add_argument('--num-video', type=int, default=5)
     ap.add_argument('--reverse', action='store_true')
+    ap.add_argument('--video', default='png', choices=list(VIDEO_MODES), help='png: numbered files (default); avi: one Motion-JPEG file per recording')
+    ap.add_argument('--jpeg-quality', type=int, default=90, help='quality 1 .. 100 of the frames of --video avi')
     args = ap.parse_args(argv)
     config = dynamically_modify_train_config(vis_config(args.dataset, args.size, overrides=dict(
         dataset=dict(path=args.path), checkpoint=args.checkpoint, num_video=args.num_video, reverse=args.reverse)))
     module = fetch_model_module(config)
     module.load_weight(config.checkpoint)
     module.to('cuda')
-    out = run_visualization(config, module, fetch_data_module(config), args.out)
+    out = run_visualization(config, module, fetch_data_module(config), args.out, video=args.video, jpeg_quality=args.jpeg_quality)
     print(json.dumps(out))
     return 0
 
