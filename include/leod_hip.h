@@ -664,6 +664,39 @@ int leod_pixel_filter_scan(const void* records, long n_events, int H, int W, lon
 int leod_survey_query(long n_events, int H, int W, int n_edges, int* tile_events, int* digit_bits, long* ws_bytes, long* state_longs);
 int leod_survey_events(const void* records, long n_events, int H, int W, const long* edges_us, int n_edges, long p_min_us, long p_max_us,
                        const unsigned char* mask, long* state, void* ws, long ws_bytes, long* io, leod_stream_t stream);
+/* Sensor fit (csrc/k_fit.hip; the rule: DESIGN.md section 1) on the same records, in stream order, t non-decreasing: events of a sensor
+ * (Hs, Ws) onto a frame (Hd, Wd).  An event with x >= Ws or y >= Hs is removed (outside).  Any other is mapped, all in integers:
+ * mirror (0 / 1): x = Ws - 1 - x; orient (0, 90, 180, 270 degrees clockwise): 90 (Hs - 1 - y, x), 180 (Ws - 1 - x, Hs - 1 - y),
+ * 270 (y, Ws - 1 - x), giving (x', y') in an image (H', W') = (Hs, Ws), or (Ws, Hs) at 90 / 270; scale k: cell (x' / k, y' / k) of the
+ * scaled image (H' / k, W' / k), an event of an incomplete edge cell is removed (cropped); place: xd = x' / k + ox, yd = y' / k + oy, an
+ * event outside [0, Wd) x [0, Hd) is removed (cropped).  reduce 0 (pick): an event is kept iff x' % k == k / 2 and y' % k == k / 2, else
+ * removed (skipped); 1 (sum): every event is kept; 2 (fire): per destination pixel an accumulator a takes the pixel's events in stream
+ * order, a += +1 (ON, bit 28) or -1 (OFF); the event that brings a to +threshold or -threshold is kept and a = 0, any other is removed
+ * (merged); threshold is read with reduce 2 only.  A kept record is stored with t and bits 28-31 unchanged and x, y replaced by xd, yd;
+ * kept records stay in stream order.  At most 2^31 - 1 events per call.
+ * Limits: Hs, Ws, Hd, Wd in [1, 16384] (so Hd * Wd <= 2^28, the bound of the per-pixel filter), k in [1, 64], |ox|, |oy| <= 16384,
+ *   threshold in [1, 32767].
+ * state: 8 + Hd * Wd longs on the device, updated in place, carried from chunk to chunk: [0] seen [1] kept [2] outside [3] cropped
+ *   [4] skipped [5] merged [6] time of the last event seen (-1: none) [7] 0; then the accumulators [Hd, Wd] (touched by reduce 2 only).
+ *   A recording starts from zeros and [6] = -1.
+ * io: as for leod_event_filter_scan.
+ * leod_event_fit_query (host only): *tile_events = records per tile (of the sort and of the compaction), *tiles_per_pass = tile counts the
+ *   scan workgroup takes per pass, *digit_bits = key bits per pass of the sort (ceil(ceil(log2(Hd * Wd)) / digit_bits) passes),
+ *   *ws_bytes = the workspace that takes n_events records in one piece (0 for reduce 0 and 1, which sort nothing), *marks_bytes = the marks
+ *   of a chunk of n_events (any may be NULL).
+ * leod_event_fit_scan: decides every record of the chunk; reduce 0 / 1: two launches, ws is not read (may be NULL); reduce 2: ws (8-byte
+ *   aligned): ws_bytes of scratch -- a chunk that needs more than it holds is cut at record boundaries into pieces of whole tiles that
+ *   fit (the workspace of one tile, leod_event_fit_query(1, ...), is the least), four launches and three per pass of the sort each;
+ *   marks (8-byte aligned) receives the chunk's decisions (class 0 = kept, as leod_event_filter_emit reads them).
+ * leod_event_fit_emit: same records, same geometry, same marks; stores the kept records in order with the mapped coordinates (out: 8-byte
+ *   aligned, capacity in records; nothing is stored at or beyond capacity), one launch.  -1 for bad arguments. */
+int leod_event_fit_query(long n_events, int Hd, int Wd, int reduce, int* tile_events, int* tiles_per_pass, int* digit_bits, long* ws_bytes,
+                         long* marks_bytes);
+int leod_event_fit_scan(const void* records, long n_events, int Hs, int Ws, int Hd, int Wd, int orient, int mirror, int k, int ox, int oy,
+                        int reduce, int threshold, long* state, void* ws, long ws_bytes, void* marks, long marks_bytes, long* io,
+                        leod_stream_t stream);
+int leod_event_fit_emit(const void* records, long n_events, int Hs, int Ws, int Hd, int Wd, int orient, int mirror, int k, int ox, int oy,
+                        int reduce, const void* marks, long marks_bytes, void* out, long capacity, leod_stream_t stream);
 
 /* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
  * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,

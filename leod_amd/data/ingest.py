@@ -31,9 +31,21 @@ burst from its second event on (``--stc-cut-trail``: the second alone), ``--anti
 whose rising edges have repeated ``--flicker-lock`` times in a row at a frequency in the band.  They run first, on whole per-pixel
 sequences, and apply the bounds and the mask; ``--denoise-us`` then sees what they keep.
 
+Sensor fit (off by default; the rule: DESIGN.md section 1; ``ops.fit_events``, csrc/k_fit.hip): ``--fit auto|K`` accepts a recording of
+any sensor size or mounting and maps its events onto the frames of ``--dataset`` -- mirror (``--fit-mirror``), quarter turns
+(``--fit-orient``), an integer scale K (auto: the largest at which the scaled image still covers the frame), an offset (``--fit-offset``,
+default centred; what leaves the frame is cropped) -- and ``--fit-reduce`` says which events of the K x K pixels of a cell survive: those
+of the centre pixel (``pick``; for K = 2 what ``ds2`` does for Gen4), all (``sum``), or one per ``--fit-threshold`` of net polarity
+(``fire``).  The source size is ``--sensor WxH``, else the header's, else the dataset's.  With a fit both containers take the streaming
+route; the filters above, the masks and ``hot_pixels.npy`` stay at the source geometry, the fit is the chain's last stage and the
+voxeliser runs at the frame geometry; the boxes take the same map (``event_filter.fit_boxes``).  Without ``--fit`` a recording of any
+other size is refused as before.
+
     python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed] [--unlabelled error|ok]
                                    [--denoise-us N] [--pixel-mask FILE.npy] [--hot-rate HZ]
                                    [--trail-us N | --stc-us N [--stc-cut-trail]] [--anti-flicker FMIN:FMAX [--flicker-lock N]]
+                                   [--sensor WxH] [--fit auto|K [--fit-offset center|X,Y] [--fit-orient 0|90|180|270] [--fit-mirror]
+                                    [--fit-reduce pick|sum|fire [--fit-threshold N]]]
 """
 import argparse
 import contextlib
@@ -56,6 +68,7 @@ SENSOR_HW = {DatasetType.GEN1: (240, 304), DatasetType.GEN4: (720, 1280)}
 DEFAULT_KEEP_CLASSES = {DatasetType.GEN1: None, DatasetType.GEN4: (0, 1, 2)}        # the three classes the Gen4 configs train on
 FRAMES_PER_COPY = 32             # windows per device call and per copy through the pinned buffer
 RAW_CHUNK_BYTES = 64 << 20       # payload bytes of a .raw file per decode call (a multiple of 4: whole EVT2 and EVT3 words)
+FIT_KEYS = ('scale', 'offset', 'orient', 'mirror', 'reduce', 'threshold')           # the options of a sensor fit: event_filter.fit_spec
 
 
 def _dataset_type(dataset_type) -> DatasetType:
@@ -65,6 +78,33 @@ def _dataset_type(dataset_type) -> DatasetType:
         return {'gen1': DatasetType.GEN1, 'gen4': DatasetType.GEN4}[str(dataset_type).lower()]
     except KeyError:
         raise ValueError(f'dataset type {dataset_type!r}: gen1 or gen4 expected') from None
+
+
+def frame_hw(dataset_type) -> Tuple[int, int]:
+    """(Hd, Wd) of the frames of a dataset: the sensor for Gen1, half of it for Gen4."""
+    dataset_type = _dataset_type(dataset_type)
+    h, w = SENSOR_HW[dataset_type]
+    return (h // 2, w // 2) if dataset_type == DatasetType.GEN4 else (h, w)
+
+
+def parse_sensor(sensor) -> Tuple[int, int]:
+    """'WxH' (as a camera's data sheet spells it) or a pair (height, width) -> (height, width), integers in [1, 16384]."""
+    if isinstance(sensor, str):
+        parts = sensor.lower().split('x')
+        if len(parts) != 2 or not all(q.strip().isdigit() for q in parts):
+            raise ValueError(f'sensor={sensor!r}: WxH expected, as in 640x480')
+        hw = (int(parts[1]), int(parts[0]))
+    else:
+        try:
+            h, w = sensor
+        except (TypeError, ValueError):
+            raise ValueError(f'sensor_hw={sensor!r}: WxH or a pair (height, width) expected') from None
+        if any(isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)) for v in (h, w)):
+            raise ValueError(f'sensor_hw={sensor!r}: integers expected')
+        hw = (int(h), int(w))
+    if not all(1 <= v <= ef.FIT_MAX_SIDE for v in hw):
+        raise ValueError(f'sensor_hw={sensor!r}: height and width in [1, {ef.FIT_MAX_SIDE}] expected')
+    return hw
 
 
 def ev_repr_name(duration_us: int, bins: int) -> str:
@@ -240,12 +280,21 @@ def _order_error(what: str, t_before: int, t_at: int) -> ValueError:
 
 
 def _report_fragment(frames: int, dropped: int, decoder: Dict, first: Optional[str] = None, tau_on: bool = False,
-                     activity: Optional[Dict] = None, pixel: Optional[Dict] = None) -> Dict:
+                     activity: Optional[Dict] = None, pixel: Optional[Dict] = None, fit: Optional[Dict] = None) -> Dict:
     """What ``voxelize_raw_recording`` returns, from plain numbers: the decoder's counters, the voxeliser's ``dropped``, ``first`` the stage
     that saw every event and applied the bounds and the mask (None: no filter; 'activity': ``ops.filter_events``; 'pixel': that op, followed
     by ``ops.filter_events`` iff ``tau_on``), ``activity`` / ``pixel`` the counters of the ops' states (None: no state yet, zeros).
-    ``kept_events`` is what reached the voxeliser, ``events`` the first stage's ``seen``, its ``outside`` joins ``dropped_events``."""
+    ``kept_events`` is what reached the voxeliser, ``events`` the first stage's ``seen``, its ``outside`` joins ``dropped_events``.
+    ``fit`` (None: no sensor fit): the counters of the state of ``ops.fit_events``, the last stage -- the first one, too, where ``first`` is
+    None; ``kept_events`` is then its ``kept``, and ``cropped_events``, ``skipped_events`` and ``merged_events`` are added."""
     rep = dict(frames=frames, dropped_events=dropped, **decoder)
+    if fit is not None:
+        if first is None:
+            rep.update(events=fit['seen'], dropped_events=dropped + fit['outside'])
+        else:
+            rep.update(_report_fragment(frames, dropped, decoder, first, tau_on, activity, pixel))
+        rep.update(kept_events=fit['kept'], cropped_events=fit['cropped'], skipped_events=fit['skipped'], merged_events=fit['merged'])
+        return rep
     if first is None:
         return rep
     fc = activity or dict(seen=0, kept=0, outside=0, masked=0, unsupported=0)
@@ -263,11 +312,19 @@ class _FilterChain:
     pixel: None or the dict of ``check_pixel_filter_options``).  Calling it on a chunk's records returns those that reach the voxeliser
     and carries the states.  With ``pixel``: ``ops.pixel_filter_events`` first, which applies the bounds and the mask and needs whole
     per-pixel sequences; ``ops.filter_events`` follows only where ``tau_us`` is set, only on a non-empty result, and without the mask.
-    Else ``ops.filter_events`` with the mask.  Times that decrease -- against the chunk before, too -- raise one ``ValueError``."""
+    Else ``ops.filter_events`` with the mask.  Times that decrease -- against the chunk before, too -- raise one ``ValueError``.
+    ``fit`` (None, or the resolved dict of ``event_filter.fit_spec`` whose source is ``sensor_hw``): the sensor fit, ``ops.fit_events``,
+    is the last stage; the stages before it work at the source geometry, and it sees what they keep (where there is none it also checks
+    the order)."""
 
-    def __init__(self, event_filter: Optional[Dict], sensor_hw, device, what: str):
+    def __init__(self, event_filter: Optional[Dict], sensor_hw, device, what: str, fit: Optional[Dict] = None):
         import torch
         self.hw, self.what, self.pstate, self.fstate = tuple(sensor_hw), what, None, None
+        self.fit, self.tstate = None, None
+        if fit is not None:
+            assert tuple(fit['src_hw']) == self.hw, 'the fit starts from the geometry the filters work at'
+            self.fit = dict(src_hw=tuple(fit['src_hw']), dst_hw=tuple(fit['frame_hw']), orient=fit['orient'], mirror=fit['mirror'],
+                            scale=fit['scale'], offset=tuple(fit['offset']), reduce=fit['reduce'], threshold=fit['threshold'])
         self.tau_us, mask, self.pixel = (event_filter[k] for k in ('tau_us', 'mask', 'pixel')) if event_filter else (None, None, None)
         self.first = None if event_filter is None else 'activity' if self.pixel is None else 'pixel'
         self.mask = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)).to(device)
@@ -276,6 +333,15 @@ class _FilterChain:
     def __call__(self, rec):
         import torch
         from leod_amd import ops
+        if self.fit is not None:
+            try:
+                if self.first is not None:
+                    rec = self._filters(rec)
+                if self.first is None or rec.shape[0]:
+                    rec, self.tstate = ops.fit_events(rec, state=self.tstate, **self.fit)
+            except ops.EventOrderError as e:
+                raise _order_error(self.what, e.t_before, e.t_at) from None
+            return rec
         if self.first is None:                                   # no stage: the order check alone, on the device
             t = rec.view(torch.int32)[:, 0].to(torch.int64) & 0xffffffff
             bad = torch.nonzero(torch.cat([t[:1] < self.t_seen, t[1:] < t[:-1]]))
@@ -285,37 +351,48 @@ class _FilterChain:
             self.t_seen = t[-1:].clone()
             return rec
         try:
-            if self.first == 'pixel':
-                rec, self.pstate = ops.pixel_filter_events(rec, *self.hw, state=self.pstate, pixel_mask=self.mask, **self.pixel)
-                if self.tau_us is not None and rec.shape[0]:
-                    rec, self.fstate = ops.filter_events(rec, *self.hw, self.tau_us, state=self.fstate)
-            else:
-                rec, self.fstate = ops.filter_events(rec, *self.hw, self.tau_us, state=self.fstate, pixel_mask=self.mask)
+            return self._filters(rec)
         except ops.EventOrderError as e:
             raise _order_error(self.what, e.t_before, e.t_at) from None
+
+    def _filters(self, rec):
+        from leod_amd import ops
+        if self.first == 'pixel':
+            rec, self.pstate = ops.pixel_filter_events(rec, *self.hw, state=self.pstate, pixel_mask=self.mask, **self.pixel)
+            if self.tau_us is not None and rec.shape[0]:
+                rec, self.fstate = ops.filter_events(rec, *self.hw, self.tau_us, state=self.fstate)
+        else:
+            rec, self.fstate = ops.filter_events(rec, *self.hw, self.tau_us, state=self.fstate, pixel_mask=self.mask)
         return rec
 
     def report(self, frames: int, dropped: int, decoder: Dict) -> Dict:
         from leod_amd import ops
+        fit = None
+        if self.fit is not None:
+            fit = ops.fit_counters(self.tstate) if self.tstate is not None else dict(seen=0, kept=0, outside=0, cropped=0, skipped=0, merged=0)
         return _report_fragment(frames, dropped, decoder, self.first, self.tau_us is not None,
                                 ops.event_filter_counters(self.fstate) if self.fstate is not None else None,
-                                ops.pixel_filter_counters(self.pstate) if self.pstate is not None else None)
+                                ops.pixel_filter_counters(self.pstate) if self.pstate is not None else None, fit)
 
 
 def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: bool, duration_us: int, bins: int, height: int, width: int,
                            ds2: bool, what: str, device=None, raw_chunk_bytes: int = RAW_CHUNK_BYTES,
-                           frames_per_copy: int = FRAMES_PER_COPY, event_filter: Optional[Dict] = None) -> Dict:
+                           frames_per_copy: int = FRAMES_PER_COPY, event_filter: Optional[Dict] = None, fit: Optional[Dict] = None) -> Dict:
     """Memory-mapped payload bytes of a .raw file -> frames appended to ``sink`` (``_NpyStream`` or, with ``packed``, a ``PackedWriter``).
     ``_RecordChunks`` brings the records of ``raw_chunk_bytes`` of payload at a time; ``_FilterChain`` (from ``event_filter``) checks the
     order of their times and hands on those that reach the voxeliser; every window that is complete -- a later event has been seen -- is
     voxelised by ``ops.voxelize_dat_windows``, the records of the last, incomplete one are carried into the next chunk.  A window that
-    loses all its events is a zero frame.  With ``event_filter`` ``encoding`` may be 'dat' (.dat record bytes).  -> ``_report_fragment``."""
+    loses all its events is a zero frame.  With ``event_filter`` or ``fit`` ``encoding`` may be 'dat' (.dat record bytes).  With ``fit``
+    (the resolved dict of ``event_filter.fit_spec``) ``height``, ``width`` are the SOURCE geometry, which the filters work at; the fit
+    is the chain's last stage and the voxeliser runs at the fit's frame geometry with ``ds2`` off.  -> ``_report_fragment``."""
     import torch
     from leod_amd import ops
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     chunks = _RecordChunks(payload, encoding, raw_chunk_bytes, device, what)
-    assert encoding != 'dat' or event_filter is not None, 'unfiltered .dat records take voxelize_recording'
-    chain = _FilterChain(event_filter, (height, width), device, what)
+    assert encoding != 'dat' or event_filter is not None or fit is not None, 'unfiltered .dat records take voxelize_recording'
+    chain = _FilterChain(event_filter, (height, width), device, what, fit=fit)
+    if fit is not None:
+        (height, width), ds2 = fit['frame_hw'], False
     D = int(duration_us)
     dropped = torch.zeros((1,), dtype=torch.int64, device=device)
     carry, done, t_last = torch.empty((0, 8), dtype=torch.uint8, device=device), 0, 0
@@ -388,6 +465,13 @@ def check_filter_options(dataset_type, denoise_us=None, pixel_mask=None, hot_rat
     """The three filter options of a call, checked on the host before anything is opened -> None when all are off, else
     dict(tau_us, mask, hot_rate_hz): ``pixel_mask`` (a ``.npy`` file name or an array) read and checked against the sensor of the
     dataset."""
+    return _filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
+
+
+def _filter_options(dataset_type, denoise_us=None, pixel_mask=None, hot_rate_hz=None, fito: Optional[Dict] = None) -> Optional[Dict]:
+    """``check_filter_options`` for a call whose sensor and fit options are ``fito`` (``check_fit_options``; None: none): the mask is
+    checked against its ``sensor_hw`` where that is given; with a fit and no ``sensor_hw`` the recording's header may state the size, so
+    any [H, W] is taken here and ``_ingest_streaming`` compares it with the source size once the file is open."""
     if denoise_us is None and pixel_mask is None and hot_rate_hz is None:
         return None
     if denoise_us is not None:
@@ -399,10 +483,55 @@ def check_filter_options(dataset_type, denoise_us=None, pixel_mask=None, hot_rat
             raise ValueError(f'hot_rate_hz={hot_rate_hz!r}: a non-negative integer rate in events per second expected')
         hot_rate_hz = int(hot_rate_hz)
     sensor = SENSOR_HW[_dataset_type(dataset_type)]
+    if fito is not None and fito['sensor_hw'] is not None:
+        sensor = fito['sensor_hw']
+    elif fito is not None and fito['fit'] is not None and pixel_mask is not None:
+        shape = np.shape(np.load(pixel_mask, allow_pickle=False) if isinstance(pixel_mask, (str, os.PathLike)) and
+                         str(pixel_mask).lower().endswith('.npy') else pixel_mask)
+        sensor = shape if len(shape) == 2 else sensor
     mask = None
     if pixel_mask is not None:
         mask = ef.read_pixel_mask(pixel_mask, sensor) if isinstance(pixel_mask, (str, os.PathLike)) else ef.check_pixel_mask(pixel_mask, sensor)
     return dict(tau_us=denoise_us, mask=mask, hot_rate_hz=hot_rate_hz)
+
+
+def check_fit_options(dataset_type, sensor_hw=None, fit=None, fit_offset=None, fit_orient=None, fit_mirror=False, fit_reduce=None,
+                      fit_threshold=None) -> Optional[Dict]:
+    """The sensor and fit options of a call, checked on the host before anything is opened -> None when all are off, else
+    dict(sensor_hw: (height, width) or None, fit: None or dict(scale, offset, orient, mirror, reduce, threshold), the keyword arguments of
+    ``event_filter.fit_spec``).  ``sensor_hw``: 'WxH' or (height, width).  ``fit``: 'auto' or the integer scale K -- the fit is on iff it
+    is given -- or such a dict (then the other ``fit_*`` stay unset).  ``fit_offset`` 'center' | 'X,Y' | (x, y), ``fit_orient`` 0 | 90 |
+    180 | 270, ``fit_mirror``, ``fit_reduce`` 'pick' | 'sum' | 'fire' and ``fit_threshold`` (only with 'fire') need ``fit``.  Without a fit
+    a sensor other than the dataset's is refused.  The options are resolved once against ``sensor_hw`` (None: the dataset's sensor) to
+    find every misuse here; the recording's own size resolves them again."""
+    if fit_mirror not in (False, True):
+        raise ValueError(f'fit_mirror={fit_mirror!r}: True or False expected')
+    others = dict(offset=fit_offset, orient=fit_orient, reduce=fit_reduce, threshold=fit_threshold)
+    given = [f'fit_{k}' for k, v in others.items() if v is not None] + (['fit_mirror'] if fit_mirror else [])
+    if sensor_hw is None and fit is None and not given:
+        return None
+    dataset_type = _dataset_type(dataset_type)
+    sensor = None if sensor_hw is None else parse_sensor(sensor_hw)
+    if fit is None:
+        if given:
+            raise ValueError(f'{", ".join(given)}: these need fit (auto or an integer scale)')
+        if sensor != tuple(SENSOR_HW[dataset_type]):
+            raise ValueError(f'sensor_hw={sensor_hw!r}: a {dataset_type.name} recording has (height, width) = {tuple(SENSOR_HW[dataset_type])}; '
+                             'another sensor needs a fit (fit=auto or an integer scale)')
+        return dict(sensor_hw=sensor, fit=None)
+    if isinstance(fit, dict):
+        if given:
+            raise ValueError(f'{", ".join(given)}: with fit given as a dict they belong in it')
+        unknown = sorted(set(fit) - set(FIT_KEYS))
+        if unknown:
+            raise ValueError(f'fit: unknown keys {unknown}; {FIT_KEYS} expected')
+        kw = dict(fit)
+    else:
+        kw = dict(scale=fit, mirror=bool(fit_mirror), **{k: v for k, v in others.items() if v is not None})
+    if kw.get('threshold') is not None and kw.get('reduce', 'pick') != 'fire':
+        raise ValueError("fit_threshold needs fit_reduce 'fire'")
+    ef.fit_spec(SENSOR_HW[dataset_type] if sensor is None else sensor, frame_hw(dataset_type), **kw)
+    return dict(sensor_hw=sensor, fit=kw)
 
 
 def check_pixel_filter_options(trail_us=None, stc_us=None, stc_cut_trail=False, anti_flicker=None, flicker_lock=None) -> Optional[Dict]:
@@ -440,11 +569,25 @@ def check_pixel_filter_options(trail_us=None, stc_us=None, stc_cut_trail=False, 
 class _TreeWriter:
     """What every route writes around its frames.  Creating it checks the header's size against the dataset's sensor (the field named as
     the container spells it) and resolves ``keep_classes``; nothing is written yet.  ``sink`` opens the frame file of the streaming
-    route, ``labels`` converts the boxes, ``finish`` writes the label files (and ``hot_pixels.npy``) and returns the base report."""
+    route, ``labels`` converts the boxes, ``finish`` writes the label files (and ``hot_pixels.npy``) and returns the base report.
+    ``fito`` (``check_fit_options``; None: no sensor or fit option): the source size is its ``sensor_hw``, else the header's, else the
+    dataset's; a header that contradicts ``sensor_hw`` is refused; with a fit ``height``, ``width`` are that source size (what the
+    filters work at), ``fit`` is the resolved ``event_filter.fit_spec`` and ``labels`` maps the boxes through it; without one the source
+    must be the dataset's sensor, as ever.  The frame file and its shape are the dataset's either way."""
 
-    def __init__(self, ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write):
+    def __init__(self, ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, fito=None):
         self.height, self.width = SENSOR_HW[dataset_type]
         names = ('height', 'width') if ev_fn.lower().endswith('.raw') else ('Height', 'Width')
+        sensor, fit = (fito['sensor_hw'], fito['fit']) if fito is not None else (None, None)
+        self.fit, self.boxes_outside = None, 0
+        if fit is not None:                                      # without one ``sensor`` is the dataset's: the check below is the one there was
+            for name, got, want in zip(names, (hdr.height, hdr.width), sensor or ()):
+                if got is not None and got != want:
+                    raise ValueError(f'{ev_fn}: header says {name} {got}, the sensor given has {want}')
+            src = sensor if sensor is not None else tuple(want if got is None else int(got)
+                                                          for got, want in zip((hdr.height, hdr.width), (self.height, self.width)))
+            self.fit = ef.fit_spec(src, frame_hw(dataset_type), **fit)
+            self.height, self.width = src
         for name, got, want in zip(names, (hdr.height, hdr.width), (self.height, self.width)):
             if got is not None and got != want:
                 raise ValueError(f'{ev_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
@@ -454,7 +597,8 @@ class _TreeWriter:
         self.ev_dir = os.path.join(out_dir, 'event_representations_v2', ev_repr_name(duration_us, bins))
         self.frame_fn = os.path.join(self.ev_dir, 'event_representations' + ('_ds2_nearest' if self.ds2 else '') +
                                      ('.evp' if self.packed else '.npy'))
-        self.frame_shape = (2 * bins,) + ((self.height // 2, self.width // 2) if self.ds2 else (self.height, self.width))
+        self.frame_shape = (2 * bins,) + (tuple(self.fit['frame_hw']) if self.fit is not None else
+                                          (self.height // 2, self.width // 2) if self.ds2 else (self.height, self.width))
 
     def makedirs(self) -> None:
         os.makedirs(self.ev_dir, exist_ok=True)
@@ -477,6 +621,8 @@ class _TreeWriter:
 
     def labels(self, n_frames: int):
         boxes = np.load(self.bbox_fn) if self.bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
+        if self.fit is not None:
+            boxes, self.boxes_outside = ef.fit_boxes(boxes, self.fit)
         return convert_labels(boxes, n_frames, self.duration_us, self.keep_classes)
 
     def finish(self, labels, n_frames: int, events: int, dropped: int, hot_mask=None) -> Dict:
@@ -489,20 +635,25 @@ class _TreeWriter:
                     boxes=int(len(lab)))
 
 
-def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix) -> Dict:
-    """A ``.raw`` file, or with ``flt`` (``check_filter_options``) or ``pix`` (``check_pixel_filter_options``) either container."""
+def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix,
+                      fito=None) -> Dict:
+    """A ``.raw`` file, or with ``flt`` (``check_filter_options``), ``pix`` (``check_pixel_filter_options``) or a fit in ``fito``
+    (``check_fit_options``) either container."""
     is_raw = ev_fn.lower().endswith('.raw')
     if is_raw:
         from leod_amd.data.utils import raw_events
         hdr, payload = raw_events.open_words(ev_fn)
         encoding = hdr.encoding
     else:
-        assert flt is not None or pix is not None, 'an unfiltered .dat recording takes voxelize_recording'
+        assert flt is not None or pix is not None or (fito is not None and fito['fit'] is not None), \
+            'an unfiltered .dat recording takes voxelize_recording'
         hdr, records = dat_events.open_records(ev_fn)
         payload, encoding = records.view(np.uint8).reshape(-1), 'dat'
-    tree = _TreeWriter(ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write)
+    tree = _TreeWriter(ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, fito)
     filtered = flt is not None or pix is not None
     tau_us, mask, hot = (flt['tau_us'], flt['mask'], None) if flt is not None else (None, None, None)
+    if mask is not None and tree.fit is not None:
+        ef.check_pixel_mask(mask, (tree.height, tree.width))     # the source size may have come from the header only now
     if flt is not None and flt['hot_rate_hz'] is not None:
         seen = count_pixel_events(payload, encoding, tree.height, tree.width, ev_fn, raw_chunk_bytes=raw_chunk_bytes)
         hot = ef.hot_pixel_mask(seen['counts'], max(seen['t_last'] - seen['t_first'], 1), flt['hot_rate_hz'])
@@ -510,7 +661,7 @@ def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, 
     event_filter = dict(tau_us=tau_us, mask=mask, pixel=pix) if filtered else None
     with tree.sink() as sink:
         res = voxelize_raw_recording(payload, encoding, sink, tree.packed, duration_us, bins, tree.height, tree.width, tree.ds2, ev_fn,
-                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter)
+                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter, fit=tree.fit)
     rep = tree.finish(tree.labels(res['frames']), res['frames'], res['events'], res['dropped_events'], hot_mask=hot)
     if is_raw:
         rep.update(early_events=res['early_events'], ignored_words=res['ignored_words'], unknown_words=res['unknown_words'],
@@ -520,6 +671,9 @@ def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, 
                    masked_pixels=int(np.count_nonzero(mask)) if mask is not None else 0)
     if pix is not None:
         rep.update(flicker_events=res['flicker_events'], burst_events=res['burst_events'])
+    if tree.fit is not None:
+        rep.update(fit=tree.fit, kept_events=res['kept_events'], cropped_events=res['cropped_events'], skipped_events=res['skipped_events'],
+                   merged_events=res['merged_events'], boxes_outside=tree.boxes_outside)
     return rep
 
 
@@ -527,7 +681,7 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
                      keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', raw_chunk_bytes: int = RAW_CHUNK_BYTES,
                      denoise_us: Optional[int] = None, pixel_mask=None, hot_rate_hz: Optional[int] = None,
                      trail_us: Optional[int] = None, stc_us: Optional[int] = None, stc_cut_trail: bool = False, anti_flicker=None,
-                     flicker_lock: Optional[int] = None) -> Dict:
+                     flicker_lock: Optional[int] = None, sensor_hw=None, fit=None) -> Dict:
     """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
     ``event_representations_ds2_nearest.npy`` at half resolution for Gen4) or, with ``write='packed'``, as the packed store of the same
     stem (``.evp``), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
@@ -543,15 +697,24 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
     ``masked_pixels``, and ``dropped_events`` is the filter's count of events outside the sensor.
     Per-pixel filters (``check_pixel_filter_options``; all off by default, and then nothing here differs): ``trail_us`` / ``stc_us`` /
     ``stc_cut_trail`` and ``anti_flicker`` / ``flicker_lock``.  They run first and apply the bounds and the mask, ``denoise_us`` then
-    sees what they keep; the report also gains ``flicker_events`` and ``burst_events``, ``kept_events`` is what reaches the voxeliser."""
+    sees what they keep; the report also gains ``flicker_events`` and ``burst_events``, ``kept_events`` is what reaches the voxeliser.
+    Sensor fit (``check_fit_options``; off by default, and then nothing here differs): ``fit`` ('auto', an integer scale, or the dict of
+    keyword arguments of ``event_filter.fit_spec``) maps a recording of another sensor size or mounting onto the frames of the dataset
+    (``ops.fit_events``, the rule: DESIGN.md section 1).  The source size is ``sensor_hw`` ('WxH' or (height, width)), else the size in
+    the file's header, else the dataset's; a header that contradicts ``sensor_hw`` is a ``ValueError``, and so is, without ``fit``, any
+    size but the dataset's.  The filters above, ``pixel_mask`` and ``hot_pixels.npy`` stay at the source geometry and the fit runs last;
+    the boxes take the same map (``event_filter.fit_boxes``); the report gains ``fit`` (the resolved options), ``cropped_events``,
+    ``skipped_events``, ``merged_events`` and ``boxes_outside``."""
     if write not in ('npy', 'packed'):
         raise ValueError(f"write={write!r}: the raw 'npy' frame file or the 'packed' store is written (an HDF5 writer is not part of "
                          'this package)')
     dataset_type = _dataset_type(dataset_type)
-    flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
+    fito = check_fit_options(dataset_type, sensor_hw, fit)
+    flt = _filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz, fito)
     pix = check_pixel_filter_options(trail_us, stc_us, stc_cut_trail, anti_flicker, flicker_lock)
-    if flt is not None or pix is not None or dat_fn.lower().endswith('.raw'):
-        return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix)
+    if flt is not None or pix is not None or (fito is not None and fito['fit'] is not None) or dat_fn.lower().endswith('.raw'):
+        return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix,
+                                 fito)
     hdr, records = dat_events.open_records(dat_fn)
     tree = _TreeWriter(dat_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write)
     offsets = dat_events.scan_windows(records, duration_us, what=dat_fn)
@@ -576,18 +739,21 @@ def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50
                  keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False, unlabelled: str = 'error',
                  raw_chunk_bytes: int = RAW_CHUNK_BYTES, denoise_us: Optional[int] = None, pixel_mask=None,
                  hot_rate_hz: Optional[int] = None, trail_us: Optional[int] = None, stc_us: Optional[int] = None,
-                 stc_cut_trail: bool = False, anti_flicker=None, flicker_lock: Optional[int] = None):
+                 stc_cut_trail: bool = False, anti_flicker=None, flicker_lock: Optional[int] = None, sensor_hw=None, fit=None):
     """Every ``<name>_td.dat`` and every ``<name>.raw`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  A recording
     without a box file raises ``FileNotFoundError`` (``unlabelled='error'``) or is written with zero labels (``'ok'``); the same name in
     both containers is a ``ValueError``.  ``denoise_us``, ``pixel_mask``, ``hot_rate_hz``: the noise filters of ``ingest_recording``, the same
     for every recording (a mask file is read once); ``trail_us``, ``stc_us``, ``stc_cut_trail``, ``anti_flicker``, ``flicker_lock``: its
-    per-pixel filters.  -> the reports, in file-name order."""
+    per-pixel filters; ``sensor_hw``, ``fit``: its sensor fit.  -> the reports, in file-name order."""
     if unlabelled not in ('error', 'ok'):
         raise ValueError(f"unlabelled={unlabelled!r}: 'error' or 'ok' expected")
-    flt = check_filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz)
+    fito = check_fit_options(dataset_type, sensor_hw, fit)
+    flt = _filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz, fito)
     filter_kw = {} if flt is None else dict(denoise_us=flt['tau_us'], pixel_mask=flt['mask'], hot_rate_hz=flt['hot_rate_hz'])
     if check_pixel_filter_options(trail_us, stc_us, stc_cut_trail, anti_flicker, flicker_lock) is not None:
         filter_kw.update(trail_us=trail_us, stc_us=stc_us, stc_cut_trail=stc_cut_trail, anti_flicker=anti_flicker, flicker_lock=flicker_lock)
+    if fito is not None:
+        filter_kw.update(sensor_hw=fito['sensor_hw'], fit=fito['fit'])
     found = {}
     for fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat')) + glob.glob(os.path.join(src_dir, '*.raw'))):
         base = os.path.basename(fn)
@@ -638,11 +804,28 @@ def main(argv=None) -> int:
                     help='remove the events of a pixel whose rising edges repeat at a frequency between FMIN and FMAX Hz (integers)')
     ap.add_argument('--flicker-lock', type=int, default=None, metavar='N',
                     help='in-band periods in a row after which a pixel counts as flickering (default 3)')
+    ap.add_argument('--sensor', default=None, metavar='WxH',
+                    help="the camera's sensor size, e.g. 640x480, where the file's header does not state it; any size but the dataset's needs --fit")
+    ap.add_argument('--fit', default=None, metavar='auto|K',
+                    help='fit the recording onto the frames of the dataset: K x K sensor pixels per frame pixel (auto: the largest K at '
+                         'which the scaled image still covers the frame)')
+    ap.add_argument('--fit-offset', default=None, metavar='center|X,Y', help='with --fit: where the scaled image lies in the frame (default center)')
+    ap.add_argument('--fit-orient', type=int, default=None, choices=[0, 90, 180, 270], help='with --fit: turn the image clockwise by so many degrees')
+    ap.add_argument('--fit-mirror', action='store_true', help='with --fit: mirror the image left to right first')
+    ap.add_argument('--fit-reduce', default=None, choices=list(ef.FIT_REDUCES),
+                    help='with --fit: of the events of K x K pixels, pick those of the centre pixel (default), sum them all, or integrate '
+                         'and fire per frame pixel')
+    ap.add_argument('--fit-threshold', type=int, default=None, metavar='N', help='with --fit-reduce fire: the firing threshold (default K * K)')
     args = ap.parse_args(argv)
     pix_kw = dict(trail_us=args.trail_us, stc_us=args.stc_us, stc_cut_trail=args.stc_cut_trail, anti_flicker=args.anti_flicker,
                   flicker_lock=args.flicker_lock)
+    fit_kw = {}
     try:
-        check_filter_options(args.dataset, args.denoise_us, args.pixel_mask, args.hot_rate)
+        fito = check_fit_options(args.dataset, args.sensor, args.fit, args.fit_offset, args.fit_orient, args.fit_mirror, args.fit_reduce,
+                                 args.fit_threshold)
+        if fito is not None:
+            fit_kw = dict(sensor_hw=fito['sensor_hw'], fit=fito['fit'])
+        _filter_options(args.dataset, args.denoise_us, args.pixel_mask, args.hot_rate, fito)
         check_pixel_filter_options(**pix_kw)
     except (ValueError, OSError) as e:
         ap.error(str(e))
@@ -652,7 +835,7 @@ def main(argv=None) -> int:
     for src, dst in pairs:
         n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
                               write=args.write, verbose=True, unlabelled=args.unlabelled, denoise_us=args.denoise_us,
-                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate, **pix_kw))
+                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate, **pix_kw, **fit_kw))
     if n == 0:
         ap.error(f'no *_td.dat or *.raw under {args.src}')
     return 0

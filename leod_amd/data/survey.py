@@ -11,7 +11,10 @@ EACH CURVE IS FOR THAT FILTER APPLIED ALONE TO THE UNFILTERED STREAM (behind the
 the per-pixel filters run first and the activity filter (``--denoise-us``) sees only what they keep, so its count there differs.
 
     python -m leod_amd.data.survey SRC --dataset gen1|gen4 [--edges-us E ...] [--anti-flicker FMIN:FMAX] [--pixel-mask FILE.npy]
-                                   [--hot-rates HZ ...] [--out REPORT.json]
+                                   [--hot-rates HZ ...] [--out REPORT.json] [--sensor WxH]
+
+``--sensor WxH`` surveys a recording of another sensor (a VGA camera, say) at its own resolution; a size in the file's header must agree
+with it.  The survey applies no sensor fit (``--fit`` of the ingestion): the ingestion's filters run before the fit, at this geometry.
 """
 import argparse
 import glob
@@ -21,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from leod_amd.data.ingest import RAW_CHUNK_BYTES, SENSOR_HW, _RecordChunks, _dataset_type, _order_error
+from leod_amd.data.ingest import RAW_CHUNK_BYTES, SENSOR_HW, _RecordChunks, _dataset_type, _order_error, parse_sensor
 from leod_amd.data.utils import dat_events, event_filter as ef
 
 # 100 us to 100 ms: the 1-2-5 steps of each decade with 3 and 7 between them, 16 edges
@@ -50,11 +53,12 @@ def check_edges(edges_us) -> List[int]:
     return edges
 
 
-def check_survey_options(dataset_type, edges_us=None, anti_flicker=None, pixel_mask=None, hot_rates=None) -> Dict:
+def check_survey_options(dataset_type, edges_us=None, anti_flicker=None, pixel_mask=None, hot_rates=None, sensor_hw=None) -> Dict:
     """The options of a call, checked on the host before anything is opened -> dict(edges, band, mask, hot_rates): ``edges_us`` None is
     ``DEFAULT_EDGES_US``; ``anti_flicker`` 'FMIN:FMAX' or (fmin, fmax) -> ``band`` (p_min_us, p_max_us) or None; ``pixel_mask`` a ``.npy``
-    file name or an array at the dataset's sensor resolution; ``hot_rates`` non-negative integer rates in events per second."""
-    sensor = SENSOR_HW[_dataset_type(dataset_type)]
+    file name or an array at the dataset's sensor resolution; ``hot_rates`` non-negative integer rates in events per second;
+    ``sensor_hw`` ('WxH' or (height, width); None: the dataset's) -> ``sensor`` (height, width), the resolution of the survey and of the mask (a key only where it is given)."""
+    sensor = SENSOR_HW[_dataset_type(dataset_type)] if sensor_hw is None else parse_sensor(sensor_hw)
     edges = check_edges(DEFAULT_EDGES_US if edges_us is None else edges_us)
     band = None if anti_flicker is None else ef.flicker_band(anti_flicker)
     mask = None
@@ -65,7 +69,10 @@ def check_survey_options(dataset_type, edges_us=None, anti_flicker=None, pixel_m
         if isinstance(r, (bool, float)) or not isinstance(r, (int, np.integer)) or int(r) < 0:
             raise ValueError(f'hot_rates: {r!r}; non-negative integer rates in events per second expected')
         rates.append(int(r))
-    return dict(edges=edges, band=band, mask=mask, hot_rates=rates)
+    opt = dict(edges=edges, band=band, mask=mask, hot_rates=rates)
+    if sensor_hw is not None:
+        opt['sensor'] = tuple(sensor)
+    return opt
 
 
 def _open_payload(ev_fn: str):
@@ -86,20 +93,23 @@ def _record_chunks(payload, encoding, raw_chunk_bytes, what):
 
 
 def survey_recording(ev_fn: str, dataset_type, edges_us=None, anti_flicker=None, pixel_mask=None, hot_rates: Optional[Sequence[int]] = None,
-                     raw_chunk_bytes: Optional[int] = None) -> Dict:
+                     raw_chunk_bytes: Optional[int] = None, sensor_hw=None) -> Dict:
     """One recording -> its report (plain Python numbers and lists, ready for JSON): recording, sensor, edges_us, band_us, the head
     counters of the survey, ``histograms`` (nb, same, sec_on, sec_off, period, run), ``removed`` (``event_filter.survey_responses``:
     denoise, trail, stc, stc_cut_trail per edge; flicker_by_lock, entry L - 1 for lock L = 1 .. 255), with ``hot_rates`` ``hot_pixels``
-    (rate -> pixels ``hot_pixel_mask`` masks, from ``ops.event_pixel_counts`` over the same chunks) and ``note``."""
+    (rate -> pixels ``hot_pixel_mask`` masks, from ``ops.event_pixel_counts`` over the same chunks) and ``note``.  ``sensor_hw``: the
+    recording's own sensor where it is not the dataset's; a size in the header that differs from it is a ``ValueError``."""
     import torch
     from leod_amd import ops
     dataset_type = _dataset_type(dataset_type)
-    opt = check_survey_options(dataset_type, edges_us, anti_flicker, pixel_mask, hot_rates)
-    height, width = SENSOR_HW[dataset_type]
+    opt = check_survey_options(dataset_type, edges_us, anti_flicker, pixel_mask, hot_rates, sensor_hw)
+    height, width = opt.get('sensor', SENSOR_HW[dataset_type])
     hdr, payload, encoding = _open_payload(ev_fn)
     names = ('height', 'width') if ev_fn.lower().endswith('.raw') else ('Height', 'Width')
     for name, got, want in zip(names, (hdr.height, hdr.width), (height, width)):
         if got is not None and got != want:
+            if sensor_hw is not None:
+                raise ValueError(f'{ev_fn}: header says {name} {got}, the sensor given has {want}')
             raise ValueError(f'{ev_fn}: header says {name} {got}, a {dataset_type.name} recording has {want}')
     edges, band = opt['edges'], opt['band']
     state, counts, mask = None, None, None
@@ -159,9 +169,11 @@ def main(argv=None) -> int:
                     help='uint8 / bool array [H, W] at sensor resolution; the events of its non-zero pixels are counted as masked')
     ap.add_argument('--hot-rates', type=int, nargs='+', default=None, metavar='HZ',
                     help='also count, per rate, the pixels --hot-rate HZ would mask')
+    ap.add_argument('--sensor', default=None, metavar='WxH', help="the recording's own sensor size, e.g. 640x480, where it is not the dataset's")
     ap.add_argument('--out', default=None, metavar='REPORT.json', help='also write the list of reports to this file')
     args = ap.parse_args(argv)
-    kw = dict(edges_us=args.edges_us, anti_flicker=args.anti_flicker, pixel_mask=args.pixel_mask, hot_rates=args.hot_rates)
+    kw = dict(edges_us=args.edges_us, anti_flicker=args.anti_flicker, pixel_mask=args.pixel_mask, hot_rates=args.hot_rates,
+              sensor_hw=args.sensor)
     try:
         check_survey_options(args.dataset, **kw)
     except (ValueError, OSError) as e:

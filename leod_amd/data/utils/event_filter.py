@@ -1,7 +1,7 @@
 """Host side of the event noise filters of the ingestion (``ops.filter_events``, csrc/k_filter.hip; ``ops.pixel_filter_events``,
 csrc/k_pixfilter.hip; the rules: DESIGN.md section 1): the hot-pixel threshold, the pixel-mask file, the band of the anti-flicker
-filter, and the response curves of a filter survey (``ops.survey_events``, csrc/k_survey.hip).  NumPy only; nothing here touches the
-device."""
+filter, the response curves of a filter survey (``ops.survey_events``, csrc/k_survey.hip), and the options and the box map of the
+sensor fit (``ops.fit_events``, csrc/k_fit.hip).  NumPy only; nothing here touches the device."""
 from typing import Tuple
 
 import numpy as np
@@ -80,6 +80,97 @@ def survey_responses(counters, edges_us) -> dict:
     flicker = np.cumsum(arr['run'][::-1])[::-1].copy()
     flicker[0] = 0
     return dict(denoise=above[1:K + 1].copy(), trail=same.copy(), stc=cand - same, stc_cut_trail=cand - second, flicker=flicker)
+
+
+FIT_REDUCES = ('pick', 'sum', 'fire')
+FIT_MAX_SIDE, FIT_MAX_SCALE, FIT_MAX_OFFSET, FIT_MAX_THRESHOLD = 16384, 64, 16384, 32767      # the limits of include/leod_hip.h
+
+
+def _fit_int(name, v, lo, hi, what):
+    if isinstance(v, str) and v.strip().lstrip('+-').isdigit():
+        v = int(v)
+    if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f'{name}={v!r}: {what} expected')
+    return int(v)
+
+
+def fit_oriented_hw(src_hw, orient: int) -> Tuple[int, int]:
+    """(H', W') of a sensor (Hs, Ws) turned by ``orient`` degrees clockwise."""
+    hs, ws = src_hw
+    return (ws, hs) if orient in (90, 270) else (hs, ws)
+
+
+def fit_spec(src_hw, frame_hw, scale='auto', offset='center', orient=0, mirror=False, reduce='pick', threshold=None) -> dict:
+    """The options of a sensor fit (the rule: DESIGN.md section 1), checked and resolved to plain ints -> dict(src_hw [Hs, Ws], frame_hw
+    [Hd, Wd], orient, mirror, scale, offset [ox, oy], reduce, threshold).  ``scale`` 'auto': the largest k with W' // k >= Wd and
+    H' // k >= Hd, or 1 when there is none ((H', W'): the sensor after ``orient``); else an integer in [1, 64].  ``offset`` 'center':
+    ox = (Wd - W' // k) // 2, oy = (Hd - H' // k) // 2, floor division; else 'X,Y' or a pair.  ``threshold`` (only with reduce 'fire';
+    None: k * k there, and None in the result for 'pick' / 'sum').  ``ValueError`` for anything else."""
+    def hw(name, v):
+        try:
+            h, w = v
+        except (TypeError, ValueError):
+            raise ValueError(f'{name}={v!r}: (height, width) expected') from None
+        return [_fit_int(name, q, 1, FIT_MAX_SIDE, f'(height, width), integers in [1, {FIT_MAX_SIDE}],') for q in (h, w)]
+    src, frame = hw('sensor_hw', src_hw), hw('frame_hw', frame_hw)
+    orient = _fit_int('fit_orient', orient, 0, 270, '0, 90, 180 or 270 (degrees clockwise)')
+    if orient % 90:
+        raise ValueError(f'fit_orient={orient!r}: 0, 90, 180 or 270 (degrees clockwise) expected')
+    if mirror not in (False, True):
+        raise ValueError(f'fit_mirror={mirror!r}: True or False expected')
+    if reduce not in FIT_REDUCES:
+        raise ValueError(f"fit_reduce={reduce!r}: 'pick', 'sum' or 'fire' expected")
+    if threshold is not None and reduce != 'fire':
+        raise ValueError("fit_threshold needs fit_reduce 'fire'")
+    ho, wo = fit_oriented_hw(src, orient)
+    if isinstance(scale, str) and scale.strip().lower() == 'auto':
+        k = max(min(wo // frame[1], ho // frame[0], FIT_MAX_SCALE), 1)       # W' // k >= Wd  <=>  k <= W' // Wd, for positive integers
+    else:
+        k = _fit_int('fit', scale, 1, FIT_MAX_SCALE, f"'auto' or an integer scale in [1, {FIT_MAX_SCALE}]")
+    if isinstance(offset, str) and offset.strip().lower() == 'center':
+        off = [(frame[1] - wo // k) // 2, (frame[0] - ho // k) // 2]
+    else:
+        parts = offset.split(',') if isinstance(offset, str) else offset
+        try:
+            ox, oy = parts
+        except (TypeError, ValueError):
+            raise ValueError(f"fit_offset={offset!r}: 'center' or X,Y expected") from None
+        off = [_fit_int('fit_offset', q, -FIT_MAX_OFFSET, FIT_MAX_OFFSET, f"'center' or X,Y, integers in [-{FIT_MAX_OFFSET}, {FIT_MAX_OFFSET}],")
+               for q in (ox, oy)]
+    if reduce == 'fire':
+        threshold = _fit_int('fit_threshold', k * k if threshold is None else threshold, 1, FIT_MAX_THRESHOLD,
+                             f'an integer in [1, {FIT_MAX_THRESHOLD}]')
+    return dict(src_hw=src, frame_hw=frame, orient=orient, mirror=bool(mirror), scale=k, offset=off, reduce=reduce, threshold=threshold)
+
+
+def fit_boxes(boxes: np.ndarray, spec: dict) -> Tuple[np.ndarray, int]:
+    """Boxes (structured array with x, y, w, h: top-left and size, continuous -- a pixel covers [x, x + 1)) of a recording at the source
+    geometry of ``spec`` (``fit_spec``) -> (the boxes at the frame geometry, the number dropped).  The same map as the events': mirror,
+    orient, divide by the scale, add the offset; then clip to the intersection of the frame and the placed scaled image; a box whose
+    clipped width or height is <= 0 is dropped.  No other filtering.  Every other field is copied."""
+    hs, ws = spec['src_hw']
+    hd, wd = spec['frame_hw']
+    k, (ox, oy) = spec['scale'], spec['offset']
+    x, y, w, h = (np.asarray(boxes[n], dtype=np.float64) for n in ('x', 'y', 'w', 'h'))
+    if spec['mirror']:
+        x = ws - (x + w)
+    if spec['orient'] == 90:
+        x, y, w, h = hs - (y + h), x, h, w
+    elif spec['orient'] == 180:
+        x, y = ws - (x + w), hs - (y + h)
+    elif spec['orient'] == 270:
+        x, y, w, h = y, ws - (x + w), h, w
+    ho, wo = fit_oriented_hw((hs, ws), spec['orient'])
+    x0, y0, x1, y1 = x / k + ox, y / k + oy, (x + w) / k + ox, (y + h) / k + oy
+    lo_x, hi_x = max(0, ox), min(wd, ox + wo // k)
+    lo_y, hi_y = max(0, oy), min(hd, oy + ho // k)
+    x0, x1 = np.clip(x0, lo_x, None), np.clip(x1, None, hi_x)
+    y0, y1 = np.clip(y0, lo_y, None), np.clip(y1, None, hi_y)
+    keep = (x1 - x0 > 0) & (y1 - y0 > 0)
+    out = boxes[keep].copy()
+    for name, v in (('x', x0), ('y', y0), ('w', x1 - x0), ('h', y1 - y0)):
+        out[name] = v[keep]
+    return out, int(len(boxes) - np.count_nonzero(keep))
 
 
 def check_pixel_mask(mask, sensor_hw: Tuple[int, int], what: str = 'pixel mask') -> np.ndarray:

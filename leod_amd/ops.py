@@ -1880,16 +1880,20 @@ def _filter_state(state, n_state, height, width):
     return state.clone()
 
 
-def _scan_and_emit(name, scan, records_u8, n, marks, marks_bytes, out):
+def _scan_and_emit(name, scan, records_u8, n, marks, marks_bytes, out, emit=None):
     """What both filters do around their scan entry point: the io block (csrc/filter_common.hpp: records emitted, first bad position,
-    the two times around it), ``scan(io)``, ONE read-back -- the kept count, or ``EventOrderError`` -- and the emit of the kept records."""
+    the two times around it), ``scan(io)``, ONE read-back -- the kept count, or ``EventOrderError`` -- and the emit of the kept records
+    (``emit(buf, m)``: an emit entry point of the caller's own; None: ``leod_event_filter_emit``, which copies them unchanged)."""
     io = torch.tensor([0, _LONG_MAX, 0, 0], dtype=torch.int64).to(records_u8.device)
     check(scan(_p(io)), f'{name} (scan)')
     m, bad, t_before, t_at = io.cpu().tolist()
     if bad != _LONG_MAX:
         raise EventOrderError(bad, t_before, t_at)
     buf = _records_out(out, m, records_u8.device, 'records the filter keeps')
-    check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), f'{name} (emit)')
+    if emit is None:
+        check(_l().leod_event_filter_emit(_p(records_u8), n, _p(marks), marks_bytes, _p(buf), m, _stream()), f'{name} (emit)')
+    else:
+        check(emit(_p(buf), m), f'{name} (emit)')
     return buf
 
 
@@ -2014,6 +2018,107 @@ def pixel_filter_events(records_u8, height, width, burst_us=None, burst_keep='fi
 def pixel_filter_counters(state):
     """The counters of a per-pixel filter state (one read-back): seen, kept, outside, masked, flicker, burst."""
     return _state_counters(state, _PIXFILTER_COUNTERS, PIXFILTER_STATE_HEAD, 'a per-pixel filter')
+
+
+# scratch of one piece of a chunk of ``fit_events`` with reduce 'fire': the sort of csrc/pixel_sort.hpp, as for ``pixel_filter_events``
+FIT_WS_BYTES = PIXFILTER_WS_BYTES
+FIT_STATE_HEAD = 8
+FIT_REDUCE = dict(pick=0, sum=1, fire=2)
+FIT_MAX_SCALE = 64
+FIT_MAX_OFFSET = 16384
+FIT_MAX_THRESHOLD = 32767
+_FIT_COUNTERS = dict(seen=0, kept=1, outside=2, cropped=3, skipped=4, merged=5)
+
+
+def _ck_hw(hw, name):
+    if not isinstance(hw, (tuple, list)) or len(hw) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384 for v in hw):
+        raise LeodHipError(f'{name}={hw!r}: (height, width), two integers in [1, 16384], expected')
+    return int(hw[0]), int(hw[1])
+
+
+def _ck_reduce(reduce):
+    if not isinstance(reduce, str) or reduce not in FIT_REDUCE:
+        raise LeodHipError(f"reduce={reduce!r}: 'pick', 'sum' or 'fire' expected")
+    return FIT_REDUCE[reduce]
+
+
+def fit_query(n_events: int, dst_hw, reduce: str = 'fire'):
+    """(records per tile, tile counts per pass of the scan workgroup, key bits per pass of the sort, workspace bytes that take ``n_events``
+    records in one piece -- 0 for 'pick' and 'sum', which sort nothing -- bytes of marks for a chunk of ``n_events``): the sensor fit's own
+    constants (csrc/k_fit.hip)."""
+    hd, wd = _ck_hw(dst_hw, 'dst_hw')
+    te, tp, db = (ctypes.c_int * 1)(), (ctypes.c_int * 1)(), (ctypes.c_int * 1)()
+    wb, mb = (ctypes.c_long * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_event_fit_query(int(n_events), hd, wd, _ck_reduce(reduce), te, tp, db, wb, mb), 'fit_query')
+    return int(te[0]), int(tp[0]), int(db[0]), int(wb[0]), int(mb[0])
+
+
+def fit_events(records_u8, src_hw, dst_hw, orient=0, mirror=False, scale=1, offset=(0, 0), reduce='pick', threshold=None, state=None,
+               out=None, ws_bytes=None):
+    """A chunk of .dat records on the device (uint8 [n * 8] or [n, 8], stream order, t non-decreasing) of a sensor ``src_hw`` = (Hs, Ws)
+    -> (kept records uint8 [m, 8] at the frame geometry ``dst_hw`` = (Hd, Wd), state) by the fit rule of DESIGN.md section 1: events
+    outside the source sensor are removed; any other is mirrored (``mirror``), turned by ``orient`` (0, 90, 180 or 270 degrees clockwise),
+    scaled by the integer ``scale`` = k (1 <= k <= 64; the cell of (x', y') is (x' // k, y' // k), incomplete edge cells are cropped) and
+    placed at ``offset`` = (ox, oy) (|ox|, |oy| <= 16384); events that leave the frame are cropped.  ``reduce``: 'pick' keeps the events
+    of the centre pixel of a cell (x' % k == k // 2 and y' % k == k // 2; the others are skipped), 'sum' keeps every event, 'fire'
+    integrates and fires per destination pixel: +1 for ON, -1 for OFF, in stream order; the event that brings the accumulator to
+    +-``threshold`` (1 <= threshold <= 32767; None: k * k; only with 'fire') is kept and resets it, any other is merged.  A kept record
+    keeps t and bits 28-31 and takes (xd, yd); kept records stay in stream order.
+    ``state`` (int64 [8 + Hd * Wd] on the device, layout in include/leod_hip.h: six counters, the last time seen, the accumulators)
+    carries the fit from chunk to chunk: None starts a recording; the given tensor is not modified, the returned one is new.  ``out``:
+    a contiguous device uint8 buffer to store the records in; it must hold them all (its first m * 8 bytes are returned as the view
+    [m, 8], nothing behind them is written).  A chunk whose times decrease -- against the chunk before, too -- raises
+    ``EventOrderError``.  ``ws_bytes`` (None: ``FIT_WS_BYTES``; only 'fire' has a workspace) bounds it: a chunk that needs more is cut into
+    pieces that fit, which changes nothing but the launches.  'pick' / 'sum': two launches; 'fire': per piece four launches and three per
+    pass of the sort; one launch to emit, one read-back (the kept count and the order verdict)."""
+    hs, ws_ = _ck_hw(src_hw, 'src_hw')
+    hd, wd = _ck_hw(dst_hw, 'dst_hw')
+    if isinstance(orient, bool) or orient not in (0, 90, 180, 270):
+        raise LeodHipError(f'orient={orient!r}: 0, 90, 180 or 270 (degrees clockwise) expected')
+    if not isinstance(mirror, bool):
+        raise LeodHipError(f'mirror={mirror!r}: True or False expected')
+    if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= FIT_MAX_SCALE:
+        raise LeodHipError(f'scale={scale!r}: an integer in [1, {FIT_MAX_SCALE}] expected')
+    if not isinstance(offset, (tuple, list)) or len(offset) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, int) or abs(v) > FIT_MAX_OFFSET for v in offset):
+        raise LeodHipError(f'offset={offset!r}: (ox, oy), two integers in [-{FIT_MAX_OFFSET}, {FIT_MAX_OFFSET}], expected')
+    red = _ck_reduce(reduce)
+    if threshold is not None and reduce != 'fire':
+        raise LeodHipError(f"threshold={threshold!r}: only reduce='fire' has a threshold")
+    if threshold is None:
+        threshold = scale * scale
+    if isinstance(threshold, bool) or not isinstance(threshold, int) or not 1 <= threshold <= FIT_MAX_THRESHOLD:
+        raise LeodHipError(f'threshold={threshold!r}: an integer in [1, {FIT_MAX_THRESHOLD}] expected')
+    records_u8, n = _ck_records(records_u8)
+    dev = records_u8.device
+    n_state = FIT_STATE_HEAD + hd * wd
+    new = _filter_state(state, n_state, hd, wd)
+    if new is None:
+        new = torch.zeros((n_state,), dtype=torch.int64, device=dev)
+        new[6] = -1
+    _, _, _, need, marks_bytes = fit_query(n, (hd, wd), reduce)
+    ws = None
+    if reduce == 'fire':
+        least = fit_query(1, (hd, wd), reduce)[3]
+        ws_bytes = FIT_WS_BYTES if ws_bytes is None else int(ws_bytes)
+        if ws_bytes < least:
+            raise LeodHipError(f'ws_bytes={ws_bytes}: at least {least} (one tile of records) expected')
+        ws_bytes = min(need, ws_bytes)
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    else:
+        ws_bytes = 0
+    marks = torch.empty((max(marks_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    geo = (hs, ws_, hd, wd, orient, int(mirror), scale, offset[0], offset[1], red)
+    scan = lambda io: _l().leod_event_fit_scan(_p(records_u8), n, *geo, threshold, _p(new), _p(ws), ws_bytes, _p(marks), marks_bytes, io,    # noqa: E731
+                                               _stream())
+    emit = lambda buf, m: _l().leod_event_fit_emit(_p(records_u8), n, *geo, _p(marks), marks_bytes, buf, m, _stream())                      # noqa: E731
+    return _scan_and_emit('fit_events', scan, records_u8, n, marks, marks_bytes, out, emit), new
+
+
+def fit_counters(state):
+    """The counters of a fit state (one read-back): seen, kept, outside, cropped, skipped, merged."""
+    return _state_counters(state, _FIT_COUNTERS, FIT_STATE_HEAD, 'a fit')
 
 
 # scratch of one piece of a chunk of ``survey_events``: the sort of csrc/pixel_sort.hpp, as for ``pixel_filter_events``
