@@ -589,6 +589,35 @@ int leod_evt_scan(const void* words, long n_words, int fmt, const long* state_in
                   leod_stream_t stream);
 int leod_evt_emit(const void* words, long n_words, int fmt, const void* ws, long ws_bytes, void* out, long capacity, long* state_out,
                   leod_stream_t stream);
+/* The way back (csrc/k_evtenc.hip; the rule: DESIGN.md section 1): the 8-byte .dat records above, in stream order, t non-decreasing ->
+ * the words of a Metavision RAW payload in the layouts above, one chunk of records per scan + emit pair.  The words of a recording are
+ * those of raw_events.encode_evt2 / encode_evt3 (leod_amd/data/utils/raw_events.py) on all its events at once, however it is cut into
+ * chunks: the stream opens with TIME_HIGH = first_time_high (fmt 3: < 4096; fmt 2: < 2^27), which the first call writes whatever its
+ * events are; TIME_HIGH where it changes (fmt 3: in steps of at most 1024) and before every high_period-th (1 .. 2^30) group; fmt 3:
+ * TIME_LOW and ADDR_Y where they change; vectors (fmt 3 only): two or more consecutive events of one t, y, p with strictly ascending x
+ * inside the 12 columns of the first are one VECT_BASE_X + VECT_12 (VECT_8 where 8 columns do).  fmt, vectors, high_period and
+ * first_time_high must be the same in every call of a recording.  With vectors the last group of a chunk is held back in the state until
+ * a later event closes it or final_chunk != 0 is given.  At most 2^31 - 1 events per call.
+ * state: 32 longs on the device, carried from chunk to chunk (all zero before the first chunk; state_out must not be state_in, which is
+ *   not modified):
+ *   [0] the opening word is written [1] [2] [3] time high (not reduced to 12 bits), time low and row of the last group written
+ *   [4] groups written (fmt 2: events) [5] events taken [6] words written [7] vector groups written [8] events held back (0 .. 12)
+ *   [9] time of the last event taken [10] words of the last call (sizes its output) [11] records of the last call with x >= 2048 or
+ *   y >= 2048, which no EVT word holds [12] position of the first of them in its chunk (-1: none) [13] position in its chunk of the first
+ *   record of the last call whose time is below that of the record before it (-1: none; 0: below the last time of the chunk before)
+ *   [14] [15] the two times around it [16] fmt [17] vectors [18] high_period [19] first_time_high [20 .. 31] the records held back.
+ *   After a call that sets [11] or [13] the state and the words are of no use.
+ * leod_evtenc_query (host only): *tile_events = events per tile, *ws_bytes = workspace for a chunk of n_events, *max_words = an upper
+ *   bound of the words n_events events take in one call (any may be NULL).
+ * leod_evtenc_scan: one memset, the marking and group-count launches (vectors only), the per-tile count and the one-workgroup scan: fills
+ *   ws and writes state_out, so state_out[10] sizes the output.
+ * leod_evtenc_emit: same arguments, same ws, the state_in of the scan; stores the words (out: 4-byte aligned, capacity in words; nothing
+ *   is stored at or beyond capacity), one launch.  records, ws: 8-byte aligned.  -1 for bad arguments. */
+int leod_evtenc_query(long n_events, int fmt, int* tile_events, long* ws_bytes, long* max_words);
+int leod_evtenc_scan(const void* records, long n_events, int fmt, int vectors, int final_chunk, long high_period, long first_time_high,
+                     const long* state_in, long* state_out, void* ws, long ws_bytes, leod_stream_t stream);
+int leod_evtenc_emit(const void* records, long n_events, int fmt, int vectors, int final_chunk, long high_period, long first_time_high,
+                     const long* state_in, const void* ws, long ws_bytes, void* out, long capacity, leod_stream_t stream);
 /* Event noise filters (csrc/k_filter.hip; the rule: DESIGN.md section 1) on the 8-byte .dat records above, in stream order, t
  * non-decreasing.  An event with x >= W or y >= H is removed (outside); one on a pixel with mask[y * W + x] != 0 is removed (masked; mask
  * may be NULL); any other is kept iff an earlier event that passed these two tests lies on one of its 8 neighbour pixels, at most tau_us

@@ -14,7 +14,7 @@ Window rule (the project's own), D = ``duration_us``:
 of windows is encoded on the device (``ops.pack_frames``) and only the packed bytes come back.
 
 An unfiltered ``.dat`` file knows its number of frames in advance (``voxelize_recording``, into an ``open_memmap``).  A ``.raw`` file (EVT2 /
-EVT3; ``data/utils/raw_events.py``), or either container with a filter on, streams through ``voxelize_raw_recording``: the chunk reader
+EVT3; ``data/utils/raw_events.py``), or either container with a filter, a fit or ``--write-events`` on, streams through ``voxelize_raw_recording``: the chunk reader
 (``_RecordChunks``: payload bytes through one pinned buffer, ``ops.decode_evt`` of csrc/k_evt.hip with the carried state), the filter chain
 (``_FilterChain``: what reaches the voxeliser, the order check, the filters' part of the report) and one loop body that cuts complete windows
 and carries the rest.  ``_TreeWriter`` writes the tree of both.  ``--unlabelled ok`` accepts recordings without a box file (zero labels).
@@ -41,11 +41,22 @@ route; the filters above, the masks and ``hot_pixels.npy`` stay at the source ge
 voxeliser runs at the frame geometry; the boxes take the same map (``event_filter.fit_boxes``).  Without ``--fit`` a recording of any
 other size is refused as before.
 
+Event file (off by default; the rule: DESIGN.md section 1; ``ops.encode_evt``, csrc/k_evtenc.hip; ``data/utils/event_writer.py``):
+``--write-events dat|evt2|evt3 --events-out DIR`` also writes the events that reach the voxeliser -- after the decoder, the filters and
+the fit -- as ``DIR[/<split>]/<name>_td.dat`` or ``DIR[/<split>]/<name>.raw`` (``--evt3-vectors``: EVT3 with vector words), at the fit's
+frame geometry where a fit is on, else the source sensor's, and the boxes as they enter ``convert_labels`` as ``<name>_bbox.npy`` beside
+it: ``DIR`` is a source directory this tool reads, so a cleaned stream can be looked at, archived, or ingested again with another window
+without the filter chain.  EVT words are made on the device, chunk by chunk, and are those of ``raw_events.encode_evt2`` /
+``encode_evt3`` on all the events at once.  With the option both containers take the streaming route; the dataset tree is byte for byte
+the one written without it.  ``DIR`` must be neither SRC nor DST; EVT holds 11 bits of x and of y, so a geometry beyond 2048 x 2048 is
+refused (``dat`` holds 14).  No Metavision tool has read a file written here.
+
     python -m leod_amd.data.ingest SRC DST --dataset gen1|gen4 [--write npy|packed] [--unlabelled error|ok]
                                    [--denoise-us N] [--pixel-mask FILE.npy] [--hot-rate HZ]
                                    [--trail-us N | --stc-us N [--stc-cut-trail]] [--anti-flicker FMIN:FMAX [--flicker-lock N]]
                                    [--sensor WxH] [--fit auto|K [--fit-offset center|X,Y] [--fit-orient 0|90|180|270] [--fit-mirror]
                                     [--fit-reduce pick|sum|fire [--fit-threshold N]]]
+                                   [--write-events dat|evt2|evt3 --events-out DIR [--evt3-vectors]]
 """
 import argparse
 import contextlib
@@ -55,7 +66,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from leod_amd.data.utils import dat_events, event_filter as ef
+from leod_amd.data.utils import dat_events, event_filter as ef, event_writer as ew
 from leod_amd.data.utils.types import DatasetType
 
 # labels.npz 'labels': the tree's 40-byte label record (data/genx_utils/labels.py reads it by field name)
@@ -377,19 +388,23 @@ class _FilterChain:
 
 def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: bool, duration_us: int, bins: int, height: int, width: int,
                            ds2: bool, what: str, device=None, raw_chunk_bytes: int = RAW_CHUNK_BYTES,
-                           frames_per_copy: int = FRAMES_PER_COPY, event_filter: Optional[Dict] = None, fit: Optional[Dict] = None) -> Dict:
+                           frames_per_copy: int = FRAMES_PER_COPY, event_filter: Optional[Dict] = None, fit: Optional[Dict] = None,
+                           events_writer=None) -> Dict:
     """Memory-mapped payload bytes of a .raw file -> frames appended to ``sink`` (``_NpyStream`` or, with ``packed``, a ``PackedWriter``).
     ``_RecordChunks`` brings the records of ``raw_chunk_bytes`` of payload at a time; ``_FilterChain`` (from ``event_filter``) checks the
     order of their times and hands on those that reach the voxeliser; every window that is complete -- a later event has been seen -- is
     voxelised by ``ops.voxelize_dat_windows``, the records of the last, incomplete one are carried into the next chunk.  A window that
     loses all its events is a zero frame.  With ``event_filter`` or ``fit`` ``encoding`` may be 'dat' (.dat record bytes).  With ``fit``
     (the resolved dict of ``event_filter.fit_spec``) ``height``, ``width`` are the SOURCE geometry, which the filters work at; the fit
-    is the chain's last stage and the voxeliser runs at the fit's frame geometry with ``ds2`` off.  -> ``_report_fragment``."""
+    is the chain's last stage and the voxeliser runs at the fit's frame geometry with ``ds2`` off.  ``events_writer`` (an
+    ``event_writer.EventFileWriter``; then an unfiltered 'dat' comes here, too): the records the chain hands on are appended to it, chunk
+    by chunk, before the carry joins them.  -> ``_report_fragment``."""
     import torch
     from leod_amd import ops
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     chunks = _RecordChunks(payload, encoding, raw_chunk_bytes, device, what)
-    assert encoding != 'dat' or event_filter is not None or fit is not None, 'unfiltered .dat records take voxelize_recording'
+    assert encoding != 'dat' or event_filter is not None or fit is not None or events_writer is not None, \
+        'unfiltered .dat records take voxelize_recording'
     chain = _FilterChain(event_filter, (height, width), device, what, fit=fit)
     if fit is not None:
         (height, width), ds2 = fit['frame_hw'], False
@@ -418,6 +433,8 @@ def voxelize_raw_recording(payload: np.ndarray, encoding: str, sink, packed: boo
                 continue
             t_last = int(rec.view(torch.int32)[-1, 0]) & 0xffffffff      # of the events SEEN, kept or not: it sets the number of frames
             rec = chain(rec)
+            if events_writer is not None:
+                events_writer.append(rec)
             rec = torch.cat([carry, rec]) if carry.shape[0] else rec
             k_last = max(-(-t_last // D) - 1, 0)                  # the window of the last event: everything before it is complete
             if k_last > done:
@@ -579,7 +596,7 @@ class _TreeWriter:
         self.height, self.width = SENSOR_HW[dataset_type]
         names = ('height', 'width') if ev_fn.lower().endswith('.raw') else ('Height', 'Width')
         sensor, fit = (fito['sensor_hw'], fito['fit']) if fito is not None else (None, None)
-        self.fit, self.boxes_outside = None, 0
+        self.fit, self.boxes_outside, self.boxes_in = None, 0, None
         if fit is not None:                                      # without one ``sensor`` is the dataset's: the check below is the one there was
             for name, got, want in zip(names, (hdr.height, hdr.width), sensor or ()):
                 if got is not None and got != want:
@@ -623,6 +640,7 @@ class _TreeWriter:
         boxes = np.load(self.bbox_fn) if self.bbox_fn is not None else np.zeros((0,), dtype=LABEL_DTYPE)
         if self.fit is not None:
             boxes, self.boxes_outside = ef.fit_boxes(boxes, self.fit)
+        self.boxes_in = boxes if self.bbox_fn is not None else None      # what --write-events writes beside the event file
         return convert_labels(boxes, n_frames, self.duration_us, self.keep_classes)
 
     def finish(self, labels, n_frames: int, events: int, dropped: int, hot_mask=None) -> Dict:
@@ -635,21 +653,85 @@ class _TreeWriter:
                     boxes=int(len(lab)))
 
 
+def check_write_options(write_events=None, events_out=None, evt3_vectors=False) -> Optional[Dict]:
+    """The options that write the kept event stream back, checked on the host before anything is opened -> None when off, else
+    dict(fmt: 'dat' | 'evt2' | 'evt3', dir, vectors).  ``write_events`` needs ``events_out`` (a directory; it is made), ``events_out``
+    and ``evt3_vectors`` need ``write_events``, ``evt3_vectors`` needs 'evt3'."""
+    if evt3_vectors not in (False, True):
+        raise ValueError(f'evt3_vectors={evt3_vectors!r}: True or False expected')
+    if write_events is None:
+        if events_out is not None or evt3_vectors:
+            raise ValueError('events_out and evt3_vectors need write_events (dat, evt2 or evt3)')
+        return None
+    if write_events not in ew.FORMATS:
+        raise ValueError(f'write_events={write_events!r}: one of {ew.FORMATS} expected')
+    if events_out is None or not isinstance(events_out, (str, os.PathLike)) or not str(events_out):
+        raise ValueError(f'write_events={write_events!r} needs events_out, the directory the event files are written to')
+    if evt3_vectors and write_events != 'evt3':
+        raise ValueError(f'evt3_vectors: only EVT3 has vector words, the format written is {write_events}')
+    return dict(fmt=write_events, dir=os.fspath(events_out), vectors=bool(evt3_vectors))
+
+
+def _check_events_dir(wev: Optional[Dict], src_dir: str, *dst_dirs: str) -> None:
+    """``ValueError`` where the event files would land among the recordings they are made from, or in a directory of the dataset tree."""
+    if wev is None:
+        return
+    real = os.path.realpath(wev['dir'])
+    if real == os.path.realpath(src_dir or '.'):
+        raise ValueError(f'events_out={wev["dir"]!r} is the source directory; the written files would join the recordings read')
+    for d in dst_dirs:
+        if real == os.path.realpath(d or '.'):
+            raise ValueError(f'events_out={wev["dir"]!r} is the destination {d!r}; the event files get a directory of their own')
+
+
+def _events_file(wev: Optional[Dict], ev_fn: str, out_dir: str, tree) -> Optional[str]:
+    """The event file of the recording ``ev_fn`` under ``wev`` (None: none), after every refusal that needs the open recording: the
+    directory, and the written geometry -- the fit's frame where a fit is on, else the source sensor's -- against the format."""
+    if wev is None:
+        return None
+    _check_events_dir(wev, os.path.dirname(ev_fn), out_dir, os.path.dirname(os.path.abspath(out_dir)))
+    ew.check_format(wev['fmt'], *_written_hw(tree), wev['vectors'])
+    base = os.path.basename(ev_fn)
+    stem = base[:-len('_td.dat')] if base.lower().endswith('_td.dat') else os.path.splitext(base)[0]
+    return os.path.join(wev['dir'], stem + ew.SUFFIX[wev['fmt']])
+
+
+def _written_hw(tree) -> Tuple[int, int]:
+    return tuple(int(v) for v in tree.fit['frame_hw']) if tree.fit is not None else (tree.height, tree.width)
+
+
+@contextlib.contextmanager
+def _events_sink(wev: Optional[Dict], events_fn: Optional[str], tree):
+    """The event file writer of a recording (None without ``wev``): closed when the body ends, aborted -- no ``.tmp`` left -- if it raises."""
+    if wev is None:
+        yield None
+        return
+    os.makedirs(wev['dir'], exist_ok=True)
+    writer = ew.EventFileWriter(events_fn, wev['fmt'], *_written_hw(tree), vectors=wev['vectors'])
+    try:
+        yield writer
+    except BaseException:
+        writer.abort()
+        raise
+    writer.close()
+
+
 def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix,
-                      fito=None) -> Dict:
-    """A ``.raw`` file, or with ``flt`` (``check_filter_options``), ``pix`` (``check_pixel_filter_options``) or a fit in ``fito``
-    (``check_fit_options``) either container."""
+                      fito=None, wev=None) -> Dict:
+    """A ``.raw`` file, or with ``flt`` (``check_filter_options``), ``pix`` (``check_pixel_filter_options``), a fit in ``fito``
+    (``check_fit_options``) or ``wev`` (``check_write_options``) either container."""
     is_raw = ev_fn.lower().endswith('.raw')
     if is_raw:
         from leod_amd.data.utils import raw_events
         hdr, payload = raw_events.open_words(ev_fn)
         encoding = hdr.encoding
     else:
-        assert flt is not None or pix is not None or (fito is not None and fito['fit'] is not None), \
+        assert flt is not None or pix is not None or (fito is not None and fito['fit'] is not None) or wev is not None, \
             'an unfiltered .dat recording takes voxelize_recording'
         hdr, records = dat_events.open_records(ev_fn)
         payload, encoding = records.view(np.uint8).reshape(-1), 'dat'
     tree = _TreeWriter(ev_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, fito)
+    events_fn = _events_file(wev, ev_fn, out_dir, tree)          # refuses before anything is written
     filtered = flt is not None or pix is not None
     tau_us, mask, hot = (flt['tau_us'], flt['mask'], None) if flt is not None else (None, None, None)
     if mask is not None and tree.fit is not None:
@@ -659,10 +741,18 @@ def _ingest_streaming(ev_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, 
         hot = ef.hot_pixel_mask(seen['counts'], max(seen['t_last'] - seen['t_first'], 1), flt['hot_rate_hz'])
         mask = hot = hot if mask is None else (mask | hot)       # hot_pixels.npy is the mask that was applied
     event_filter = dict(tau_us=tau_us, mask=mask, pixel=pix) if filtered else None
-    with tree.sink() as sink:
+    with tree.sink() as sink, _events_sink(wev, events_fn, tree) as writer:
         res = voxelize_raw_recording(payload, encoding, sink, tree.packed, duration_us, bins, tree.height, tree.width, tree.ds2, ev_fn,
-                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter, fit=tree.fit)
+                                     raw_chunk_bytes=raw_chunk_bytes, event_filter=event_filter, fit=tree.fit, events_writer=writer)
+    if not is_raw and not filtered and tree.fit is None:         # here for the event file alone: no stage has counted the events
+        res['events'] = int(hdr.n_events)
     rep = tree.finish(tree.labels(res['frames']), res['frames'], res['events'], res['dropped_events'], hot_mask=hot)
+    if writer is not None:
+        if tree.boxes_in is not None:
+            np.save(events_fn[:-len(ew.SUFFIX[wev['fmt']])] + '_bbox.npy', tree.boxes_in)
+        rep.update(events_file=events_fn, written_events=writer.events, written_bytes=os.path.getsize(events_fn))
+        if wev['fmt'] != 'dat':
+            rep.update(written_words=writer.words)
     if is_raw:
         rep.update(early_events=res['early_events'], ignored_words=res['ignored_words'], unknown_words=res['unknown_words'],
                    clock_wraps=res['wraps'])
@@ -681,7 +771,8 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
                      keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', raw_chunk_bytes: int = RAW_CHUNK_BYTES,
                      denoise_us: Optional[int] = None, pixel_mask=None, hot_rate_hz: Optional[int] = None,
                      trail_us: Optional[int] = None, stc_us: Optional[int] = None, stc_cut_trail: bool = False, anti_flicker=None,
-                     flicker_lock: Optional[int] = None, sensor_hw=None, fit=None) -> Dict:
+                     flicker_lock: Optional[int] = None, sensor_hw=None, fit=None, write_events: Optional[str] = None, events_out=None,
+                     evt3_vectors: bool = False) -> Dict:
     """One recording -> ``out_dir`` in the dataset layout: frames as the raw ``.npy`` twin (``event_representations.npy`` for Gen1,
     ``event_representations_ds2_nearest.npy`` at half resolution for Gen4) or, with ``write='packed'``, as the packed store of the same
     stem (``.evp``), ``objframe_idx_2_repr_idx.npy``, ``labels_v2/labels.npz``.
@@ -704,7 +795,15 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
     the file's header, else the dataset's; a header that contradicts ``sensor_hw`` is a ``ValueError``, and so is, without ``fit``, any
     size but the dataset's.  The filters above, ``pixel_mask`` and ``hot_pixels.npy`` stay at the source geometry and the fit runs last;
     the boxes take the same map (``event_filter.fit_boxes``); the report gains ``fit`` (the resolved options), ``cropped_events``,
-    ``skipped_events``, ``merged_events`` and ``boxes_outside``."""
+    ``skipped_events``, ``merged_events`` and ``boxes_outside``.
+    Event file (``check_write_options``; off by default, and then nothing here differs): ``write_events`` 'dat' | 'evt2' | 'evt3' writes
+    the events that reach the voxeliser -- after the filters and the fit -- to ``events_out/<name>_td.dat`` or ``events_out/<name>.raw``
+    (``event_writer.EventFileWriter``; EVT words come from ``ops.encode_evt`` on the device, ``evt3_vectors``: with vector words), at the
+    fit's frame geometry where a fit is on, else the source sensor's, and the boxes as they enter ``convert_labels`` to
+    ``events_out/<name>_bbox.npy``: ``events_out`` is a source directory this function reads.  Both containers then take the streaming
+    route; the tree is byte for byte the one written without the option.  ``events_out`` must not be the source directory, ``out_dir`` or
+    its parent; a geometry beyond 2048 x 2048 does not fit EVT.  The report gains ``events_file``, ``written_events``, ``written_bytes``
+    and, for EVT, ``written_words``."""
     if write not in ('npy', 'packed'):
         raise ValueError(f"write={write!r}: the raw 'npy' frame file or the 'packed' store is written (an HDF5 writer is not part of "
                          'this package)')
@@ -712,9 +811,11 @@ def ingest_recording(dat_fn: str, bbox_fn: Optional[str], out_dir: str, dataset_
     fito = check_fit_options(dataset_type, sensor_hw, fit)
     flt = _filter_options(dataset_type, denoise_us, pixel_mask, hot_rate_hz, fito)
     pix = check_pixel_filter_options(trail_us, stc_us, stc_cut_trail, anti_flicker, flicker_lock)
-    if flt is not None or pix is not None or (fito is not None and fito['fit'] is not None) or dat_fn.lower().endswith('.raw'):
+    wev = check_write_options(write_events, events_out, evt3_vectors)
+    if flt is not None or pix is not None or (fito is not None and fito['fit'] is not None) or wev is not None or \
+            dat_fn.lower().endswith('.raw'):
         return _ingest_streaming(dat_fn, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write, raw_chunk_bytes, flt, pix,
-                                 fito)
+                                 fito, wev)
     hdr, records = dat_events.open_records(dat_fn)
     tree = _TreeWriter(dat_fn, hdr, bbox_fn, out_dir, dataset_type, duration_us, bins, keep_classes, write)
     offsets = dat_events.scan_windows(records, duration_us, what=dat_fn)
@@ -739,12 +840,14 @@ def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50
                  keep_classes: Optional[Sequence[int]] = None, write: str = 'npy', verbose: bool = False, unlabelled: str = 'error',
                  raw_chunk_bytes: int = RAW_CHUNK_BYTES, denoise_us: Optional[int] = None, pixel_mask=None,
                  hot_rate_hz: Optional[int] = None, trail_us: Optional[int] = None, stc_us: Optional[int] = None,
-                 stc_cut_trail: bool = False, anti_flicker=None, flicker_lock: Optional[int] = None, sensor_hw=None, fit=None):
+                 stc_cut_trail: bool = False, anti_flicker=None, flicker_lock: Optional[int] = None, sensor_hw=None, fit=None,
+                 write_events: Optional[str] = None, events_out=None, evt3_vectors: bool = False):
     """Every ``<name>_td.dat`` and every ``<name>.raw`` of ``src_dir`` with its ``<name>_bbox.npy`` -> ``dst_dir/<name>/``.  A recording
     without a box file raises ``FileNotFoundError`` (``unlabelled='error'``) or is written with zero labels (``'ok'``); the same name in
     both containers is a ``ValueError``.  ``denoise_us``, ``pixel_mask``, ``hot_rate_hz``: the noise filters of ``ingest_recording``, the same
     for every recording (a mask file is read once); ``trail_us``, ``stc_us``, ``stc_cut_trail``, ``anti_flicker``, ``flicker_lock``: its
-    per-pixel filters; ``sensor_hw``, ``fit``: its sensor fit.  -> the reports, in file-name order."""
+    per-pixel filters; ``sensor_hw``, ``fit``: its sensor fit; ``write_events``, ``events_out``, ``evt3_vectors``: its event files, all in
+    the one directory ``events_out``, which must be neither ``src_dir`` nor ``dst_dir``.  -> the reports, in file-name order."""
     if unlabelled not in ('error', 'ok'):
         raise ValueError(f"unlabelled={unlabelled!r}: 'error' or 'ok' expected")
     fito = check_fit_options(dataset_type, sensor_hw, fit)
@@ -754,6 +857,10 @@ def ingest_split(src_dir: str, dst_dir: str, dataset_type, duration_us: int = 50
         filter_kw.update(trail_us=trail_us, stc_us=stc_us, stc_cut_trail=stc_cut_trail, anti_flicker=anti_flicker, flicker_lock=flicker_lock)
     if fito is not None:
         filter_kw.update(sensor_hw=fito['sensor_hw'], fit=fito['fit'])
+    wev = check_write_options(write_events, events_out, evt3_vectors)
+    if wev is not None:
+        _check_events_dir(wev, src_dir, dst_dir)
+        filter_kw.update(write_events=wev['fmt'], events_out=wev['dir'], evt3_vectors=wev['vectors'])
     found = {}
     for fn in sorted(glob.glob(os.path.join(src_dir, '*_td.dat')) + glob.glob(os.path.join(src_dir, '*.raw'))):
         base = os.path.basename(fn)
@@ -816,6 +923,13 @@ def main(argv=None) -> int:
                     help='with --fit: of the events of K x K pixels, pick those of the centre pixel (default), sum them all, or integrate '
                          'and fire per frame pixel')
     ap.add_argument('--fit-threshold', type=int, default=None, metavar='N', help='with --fit-reduce fire: the firing threshold (default K * K)')
+    ap.add_argument('--write-events', default=None, choices=list(ew.FORMATS), metavar='FMT',
+                    help='also write the events that reach the voxeliser, after the filters and the fit, as a .dat file (dat) or a '
+                         'Metavision .raw file (evt2, evt3) per recording; needs --events-out')
+    ap.add_argument('--events-out', default=None, metavar='DIR',
+                    help='with --write-events: the directory of the event files and their box files (DIR/<split>/ where SRC holds splits); '
+                         'neither SRC nor DST; it is itself a source directory this tool reads')
+    ap.add_argument('--evt3-vectors', action='store_true', help='with --write-events evt3: write runs of events in one row as vector words')
     args = ap.parse_args(argv)
     pix_kw = dict(trail_us=args.trail_us, stc_us=args.stc_us, stc_cut_trail=args.stc_cut_trail, anti_flicker=args.anti_flicker,
                   flicker_lock=args.flicker_lock)
@@ -827,15 +941,18 @@ def main(argv=None) -> int:
             fit_kw = dict(sensor_hw=fito['sensor_hw'], fit=fito['fit'])
         _filter_options(args.dataset, args.denoise_us, args.pixel_mask, args.hot_rate, fito)
         check_pixel_filter_options(**pix_kw)
+        wev = check_write_options(args.write_events, args.events_out, args.evt3_vectors)
     except (ValueError, OSError) as e:
         ap.error(str(e))
     splits = [s for s in ('train', 'val', 'test') if os.path.isdir(os.path.join(args.src, s))]
     pairs = [(os.path.join(args.src, s), os.path.join(args.dst, s)) for s in splits] or [(args.src, args.dst)]
     n = 0
-    for src, dst in pairs:
+    for split, (src, dst) in zip(splits or [None], pairs):
+        wev_kw = {} if wev is None else dict(write_events=wev['fmt'], evt3_vectors=wev['vectors'],
+                                             events_out=os.path.join(wev['dir'], split) if split else wev['dir'])
         n += len(ingest_split(src, dst, args.dataset, duration_us=args.duration_us, bins=args.bins, keep_classes=args.keep_classes,
                               write=args.write, verbose=True, unlabelled=args.unlabelled, denoise_us=args.denoise_us,
-                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate, **pix_kw, **fit_kw))
+                              pixel_mask=args.pixel_mask, hot_rate_hz=args.hot_rate, **pix_kw, **fit_kw, **wev_kw))
     if n == 0:
         ap.error(f'no *_td.dat or *.raw under {args.src}')
     return 0

@@ -1814,6 +1814,85 @@ def evt_state_counters(state):
     return _state_counters(state, _EVT_COUNTERS)
 
 
+EVT_ENC_STATE_LONGS = 32
+EVT_ENC_HOLD = 12                # the most events a state holds back: one group of a vector stream
+EVT_ENC_FIRST_HIGH_LIMIT = {2: 1 << 27, 3: 4096}
+EVT_ENC_PERIOD_LIMIT = 1 << 30
+_EVT_ENC_COUNTERS = dict(events=5, words=6, groups=4, vector_groups=7, held=8)
+
+
+def evt_encode_query(n_events: int = 0, fmt='evt3'):
+    """(events per tile, workspace bytes for a chunk of ``n_events`` events, an upper bound of the words ``n_events`` events take in one
+    call): the encoder's own constants (csrc/k_evtenc.hip)."""
+    if fmt not in EVT_FORMATS or isinstance(fmt, bool):
+        raise LeodHipError(f'encoding {fmt!r}: evt2 or evt3 expected')
+    te, ws, mw = (ctypes.c_int * 1)(), (ctypes.c_long * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_evtenc_query(int(n_events), EVT_FORMATS[fmt], te, ws, mw), 'evt_encode_query')
+    return int(te[0]), int(ws[0]), int(mw[0])
+
+
+def encode_evt(records_u8, fmt, state=None, final=False, vectors=False, high_period=64, first_time_high=0, out=None):
+    """A chunk of .dat records on the device (uint8 [n * 8] or [n, 8], stream order, t non-decreasing) -> (words uint8 [n_words *
+    word bytes], state): the next words of the Metavision RAW payload (EVT2 u32 words or EVT3 u16 words, as they lie in a file) that
+    ``raw_events.encode_evt2`` / ``encode_evt3`` write for ALL the events of the recording at once, however it is cut into chunks
+    (DESIGN.md section 1).  ``state`` (int64 [32] on the device, layout in include/leod_hip.h) carries the encoder from chunk to chunk:
+    None starts a recording -- that call writes the opening TIME_HIGH = ``first_time_high`` whatever its events are; the given tensor is
+    not modified, the returned one is new.  ``vectors`` (evt3 only), ``high_period`` and ``first_time_high`` must be the same in every
+    call of a recording.  With ``vectors`` the last group of a chunk (at most 12 records) is held back in the state until a later event
+    closes it; ``final=True`` writes it out (an empty chunk with ``final`` flushes).  ``out``: a contiguous device uint8 buffer to store
+    the words in; it must hold them all (its first bytes are returned as a view, nothing behind them is written).  A record with
+    x >= 2048 or y >= 2048, which no EVT word holds, raises ``LeodHipError`` naming its position; a chunk whose times decrease --
+    against the chunk before, too -- raises ``EventOrderError``.  One memset, two to four launches, one read-back (the new state), one
+    launch to emit."""
+    if fmt not in EVT_FORMATS or isinstance(fmt, bool):
+        raise LeodHipError(f'encoding {fmt!r}: evt2 or evt3 expected')
+    fmt = EVT_FORMATS[fmt]
+    if vectors not in (False, True) or final not in (False, True):
+        raise LeodHipError(f'vectors={vectors!r}, final={final!r}: True or False expected')
+    if vectors and fmt != 3:
+        raise LeodHipError('vectors: only EVT3 has vector words')
+    if isinstance(high_period, bool) or not isinstance(high_period, int) or not 1 <= high_period <= EVT_ENC_PERIOD_LIMIT:
+        raise LeodHipError(f'high_period={high_period!r}: an integer in [1, 2^30] expected')
+    if isinstance(first_time_high, bool) or not isinstance(first_time_high, int) or not 0 <= first_time_high < EVT_ENC_FIRST_HIGH_LIMIT[fmt]:
+        raise LeodHipError(f'first_time_high={first_time_high!r}: an integer in [0, {EVT_ENC_FIRST_HIGH_LIMIT[fmt]}) expected for EVT{fmt}')
+    records_u8, n = _ck_records(records_u8)
+    dev = records_u8.device
+    if state is None:
+        state = torch.zeros((EVT_ENC_STATE_LONGS,), dtype=torch.int64, device=dev)
+    _ck(state, torch.int64, 'state')
+    if state.numel() != EVT_ENC_STATE_LONGS:
+        raise LeodHipError(f'state: {EVT_ENC_STATE_LONGS} int64 expected, got {tuple(state.shape)}')
+    ws_bytes = evt_encode_query(n, fmt)[1]
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    new = torch.empty_like(state)
+    args = (_p(records_u8), n, fmt, int(vectors), int(final), high_period, first_time_high, _p(state))
+    check(_l().leod_evtenc_scan(*args, _p(new), _p(ws), ws_bytes, _stream()), 'encode_evt (scan)')
+    host = new.cpu().tolist()
+    if host[13] >= 0:
+        raise EventOrderError(host[13], host[14], host[15])
+    if host[11]:
+        r = records_u8.reshape(-1, 8)[host[12]].view(torch.int32)[1].item()
+        raise LeodHipError(f'records: event {host[12]} of the chunk (event {host[5] - n + host[12]} of the recording) lies at x = {r & 16383}, '
+                           f'y = {(r >> 14) & 16383}; an EVT{fmt} word holds 11 bits of each ({host[11]} such records in the chunk)')
+    n_words, wb = host[10], EVT_WORD_BYTES[fmt]
+    if out is None:
+        buf = torch.empty((n_words * wb,), dtype=torch.uint8, device=dev)
+    else:
+        _ck(out, torch.uint8, 'out')
+        if out.numel() < n_words * wb:
+            raise LeodHipError(f'out: {out.numel()} bytes do not hold the {n_words} words of the chunk')
+        if out.data_ptr() % 4:
+            raise LeodHipError('out: a 4-byte aligned buffer expected')
+        buf = out.reshape(-1)[:n_words * wb]
+    check(_l().leod_evtenc_emit(*args, _p(ws), ws_bytes, _p(buf), n_words, _stream()), 'encode_evt (emit)')
+    return buf, new
+
+
+def evt_encode_counters(state):
+    """The counters of an encoder state (one read-back): events taken, words and groups written, vector_groups among them, events held."""
+    return _state_counters(state, _EVT_ENC_COUNTERS, EVT_ENC_STATE_LONGS, 'an encoder')
+
+
 # scratch of one piece of a chunk of ``filter_events`` (the (slot, pixel) table of csrc/k_filter.hip): 64 MiB takes 2^21 records in one
 # piece.  Sweep in DESIGN.md section 4 (profiles/r11_a_kbench_filter.txt, SYNTHETIC recording): 1 MiB is 5x slower, 16 MiB 13 %, 32 MiB 5 %;
 # 64 MiB is within 4 % of the fastest bound (256 MiB, a whole 64 MiB chunk of records in one piece) at a quarter of its memory
