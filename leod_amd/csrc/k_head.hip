@@ -477,7 +477,10 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
             const float dl_diou = -2.f * iou;
             const float diou_dI = (u + area_i) / (u * u), diou_dP = -area_i / (u * u);
             const float dI_dtlx = -ih * en, dI_dbrx = ih * en, dI_dtly = -iw * en, dI_dbry = iw * en;
-            const float al = p_l > t_l ? 1.f : 0.f, ar = p_r < t_r ? 1.f : 0.f, at = p_t > t_t ? 1.f : 0.f, ab = p_b < t_b ? 1.f : 0.f;
+            // share of the max / min gradient that goes to the prediction: torch.max / torch.min split it evenly at equality, so an edge
+            // that coincides with the label's takes half the term (a prediction equal to its label then has zero box gradient)
+            auto share = [](float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); };
+            const float al = share(p_l, t_l), ar = share(t_r, p_r), at = share(p_t, t_t), ab = share(t_b, p_b);
             const float dI_dpx = dI_dtlx * al + dI_dbrx * ar, dI_dpy = dI_dtly * at + dI_dbry * ab;
             const float dI_dpw = -0.5f * dI_dtlx * al + 0.5f * dI_dbrx * ar, dI_dph = -0.5f * dI_dtly * at + 0.5f * dI_dbry * ab;
             const float k = reg_w * inv_fg_mean * dl_diou * gscale * bw;

@@ -634,6 +634,7 @@ def test_state_plumbing_multi_buffer_kernels(ops):
 
 
 # ---------------------------------------------------------------------------------------------------
+# ties and thresholds of the head tail (equal costs / IoUs / scores, values exactly on a boundary): tests/test_head_exact_gpu.py
 HEAD_GEOMS = {'gen1': ((256, 320), (240, 304), 2), 'gen4': ((384, 640), (360, 640), 3), '1mpx': ((768, 1280), (720, 1280), 3)}
 
 
