@@ -145,6 +145,9 @@ dwconv_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x, f
 
 static inline bool dw_geom(DwGeom& g, int B, int H, int W, int C, int ks, int stride, int pad) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || ks < 1 || ks > 15 || stride < 1 || pad < 0) return false;
+    // a kernel larger than the padded map has no output: refused here, because the truncating division below turns
+    // (H + 2 * pad - ks) in (-stride, 0) into 0 and would report one output row
+    if (ks > H + 2 * pad || ks > W + 2 * pad) return false;
     g = DwGeom{B, H, W, C, (H + 2 * pad - ks) / stride + 1, (W + 2 * pad - ks) / stride + 1, ks, stride, pad};
     return g.Ho > 0 && g.Wo > 0;
 }
