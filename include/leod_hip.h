@@ -726,6 +726,39 @@ int leod_event_fit_scan(const void* records, long n_events, int Hs, int Ws, int 
                         leod_stream_t stream);
 int leod_event_fit_emit(const void* records, long n_events, int Hs, int Ws, int Hd, int Wd, int orient, int mirror, int k, int ox, int oy,
                         int reduce, const void* marks, long marks_bytes, void* out, long capacity, leod_stream_t stream);
+/* Video-to-events simulator (csrc/k_simulate.hip; the rule: DESIGN.md section 1): luma frames (uint8 [n_frames, H, W] on the device) with
+ * their times (times_us: device long [n_frames], strictly increasing, above the time the state carries, below 2^32) -> .dat records, all
+ * in integers.  lut (device int [256], values in [0, 2^24)) is the response table, theta_on / theta_off (device int [H, W], >= 1) the
+ * thresholds.  Per pixel: a reference level m, the time t_keep of its last kept event (-1: none), the byte of the last frame.  The first
+ * frame of a recording sets m = lut[v] and emits nothing.  Any later frame at t1, after one at t0, with l0 = lut[v before], l1 = lut[v],
+ * D = t1 - t0: l1 > l0: for j = 1, 2, ... while m + j * theta_on <= l1 an ON candidate at t = t0 + max(1, D * (m + j * theta_on - l0) /
+ * (l1 - l0)), then m += n * theta_on; l1 < l0: the same with OFF, levels m - j * theta_off >= l1, t = t0 + max(1, D * (l0 - (m - j *
+ * theta_off)) / (l0 - l1)); l1 == l0: nothing.  A candidate is kept unless t_keep >= 0 and t - t_keep < refractory_us; a kept one sets
+ * t_keep = t, a dropped one is counted and still moves m.  The records (t u32, x bits 0-13, y bits 14-27, ON = bit 28) come out ordered
+ * by t, then pixel y * W + x, then j.  The caller checks the values (ops.simulate_check): the device clamps what would leave a buffer.
+ * Limits: H, W in [1, 16384], H * W < 2^30, n_frames <= 65536 per call, refractory_us in [0, 2^32), (max lut - min lut) / min theta <=
+ *   4096 (at most 4097 candidates per pixel and interval, as m may lag the value by theta - 1), at most 2^31 - 1 events per call.
+ * state: *state_longs longs on the device, updated in place by leod_simulate_emit alone, carried from call to call: [0] frames seen
+ *   [1] kept events [2] ON [3] OFF [4] refractory-dropped [5] time of the last frame (-1: none) [6], [7] 0; then {m, t_keep} per pixel;
+ *   then the last frame's bytes, padded with zeros to a whole long.  A recording starts from zeros, [5] = -1 and every t_keep = -1.
+ * counts: *count_longs + n_frames longs on the device (8-byte aligned), written by leod_simulate_count and read by leod_simulate_emit
+ *   of the same arguments: kept events per tile of pixels, per pixel (32 bits each), and behind them per interval: counts[*count_longs
+ *   + k] = the kept events of the interval that ends at frame k of the call (0 for the first frame of a recording).
+ * leod_simulate_query (host only): *tile_pixels = pixels per tile (one lane a pixel), *digit_bits = key bits per pass of the sort
+ *   (ceil(ceil(log2(t_end - t_base)) / digit_bits) passes), *state_longs, *count_longs as above, *ws_bytes = the workspace of a call that
+ *   keeps n_events events (any may be NULL).
+ * leod_simulate_count: one memset and one launch; writes counts, nothing else.
+ * leod_simulate_emit: n_events = the sum of the call's interval counts, t_base = the time of the frame before the call's first interval
+ *   (state [5], or times_us[0] for the first call of a recording), t_end = times_us[n_frames - 1]; ws (8-byte aligned, ws_bytes >= the
+ *   query's; not read for n_events = 0); out: 8-byte aligned, capacity >= n_events records.  Four launches and three per pass of the
+ *   sort (n_events = 0: three launches).  -1 for bad arguments. */
+int leod_simulate_query(long n_events, int H, int W, int* tile_pixels, int* digit_bits, long* state_longs, long* count_longs,
+                        long* ws_bytes);
+int leod_simulate_count(const unsigned char* frames, int n_frames, int H, int W, const long* times_us, const int* lut, const int* theta_on,
+                        const int* theta_off, long refractory_us, const long* state, long* counts, leod_stream_t stream);
+int leod_simulate_emit(const unsigned char* frames, int n_frames, int H, int W, const long* times_us, const int* lut, const int* theta_on,
+                       const int* theta_off, long refractory_us, long* state, long* counts, long t_base, long t_end, long n_events,
+                       void* ws, long ws_bytes, void* out, long capacity, leod_stream_t stream);
 
 /* Packed event frames (csrc/k_pack.hip; format: leod_amd/data/utils/packed.py).  A frame of E = C*H*W bytes is a blob:
  * {u32 n_masks, u32 n_values, 8 zero bytes}, ceil(E/4096) group entries {u64 l1, u32 mask_base, u32 value_base}, n_masks u64 block masks,

@@ -2200,6 +2200,166 @@ def fit_counters(state):
     return _state_counters(state, _FIT_COUNTERS, FIT_STATE_HEAD, 'a fit')
 
 
+# the video-to-events simulator (csrc/k_simulate.hip; the rule: DESIGN.md section 1)
+SIM_STATE_HEAD = 8
+SIM_MAX_FRAMES = 65536           # per call
+SIM_LUT_LIMIT = 1 << 24
+SIM_MAX_CANDIDATES = 4096        # (max lut - min lut) // min theta: candidates per pixel and interval
+SIM_T_LIMIT = 1 << 32            # the .dat clock
+SIM_MAX_EVENTS = (1 << 31) - 1   # per piece of a call: the sort's positions
+_SIM_COUNTERS = dict(frames=0, kept=1, on=2, off=3, dropped=4, t_last=5)
+
+
+def simulate_query(n_events: int, height: int, width: int):
+    """(pixels per tile -- a lane takes a pixel --, key bits per pass of the sort, int64 words of the state block, int64 words of the count
+    block before its per-frame counts, workspace bytes of a call that keeps ``n_events`` events): the simulator's own constants
+    (csrc/k_simulate.hip)."""
+    tp, db = (ctypes.c_int * 1)(), (ctypes.c_int * 1)()
+    sl, cl, wb = (ctypes.c_long * 1)(), (ctypes.c_long * 1)(), (ctypes.c_long * 1)()
+    check(_l().leod_simulate_query(int(n_events), int(height), int(width), tp, db, sl, cl, wb), 'simulate_query')
+    return int(tp[0]), int(db[0]), int(sl[0]), int(cl[0]), int(wb[0])
+
+
+def simulate_check(height, width, times_us, lut, theta_on, theta_off, refractory_us=0, t_last=-1):
+    """Every limit of the simulator's rule, on the HOST (no device is touched): ``ValueError``, else (times int64
+    [n], lut int32 [256], theta_on int32 [H, W], theta_off int32 [H, W]) as numpy arrays.  H, W in [1, 16384] with H * W < 2^30; ``lut``
+    256 integers in [0, 2^24); thresholds (an integer, or an integer array [H, W]) >= 1; (max lut - min lut) // the least threshold <=
+    4096; ``refractory_us`` in [0, 2^32); ``times_us`` integers in [0, 2^32), strictly increasing and above ``t_last``."""
+    import numpy as np
+    for name, v in (('height', height), ('width', width)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 16384:
+            raise ValueError(f'{name}={v!r}: an integer in [1, 16384] expected')
+    height, width = int(height), int(width)
+    if height * width >= 1 << 30:
+        raise ValueError(f'{height} x {width} pixels: fewer than 2^30 expected (pixel * 2 + polarity is a 32-bit value of the sort)')
+
+    def ints(v, name, shape):
+        if isinstance(v, torch.Tensor):
+            if v.is_cuda:
+                raise ValueError(f'{name}: host data expected (it is checked here, then uploaded), got a tensor on {v.device}')
+            v = v.numpy()
+        a = np.asarray(v)
+        if a.size == 0 and shape is None:
+            a = a.astype(np.int64)                               # an empty list has no type of its own
+        if a.dtype == np.bool_ or a.dtype.kind not in 'iu':
+            raise ValueError(f'{name}: integers expected, got {a.dtype}')
+        if shape is not None and a.ndim == 0:
+            a = np.full(shape, a)
+        if shape is not None and a.shape != shape:
+            raise ValueError(f'{name}: shape {a.shape}, expected {shape}')
+        return a.astype(np.int64)
+    lut = ints(lut, 'lut', None).reshape(-1)
+    if lut.shape != (256,) or lut.min() < 0 or lut.max() >= SIM_LUT_LIMIT:
+        raise ValueError('lut: 256 integers in [0, 2^24) expected')
+    th = []
+    for name, v in (('theta_on', theta_on), ('theta_off', theta_off)):
+        a = ints(v, name, (height, width))
+        if a.min() < 1 or a.max() >= 1 << 31:
+            raise ValueError(f'{name}: thresholds in [1, 2^31) expected, got [{int(a.min())}, {int(a.max())}]')
+        th.append(a)
+    least = int(min(th[0].min(), th[1].min()))
+    span = int(lut.max() - lut.min())
+    if span // least > SIM_MAX_CANDIDATES:
+        raise ValueError(f'the table spans {span} and the least threshold is {least}: {span // least} candidates per pixel and interval, '
+                         f'at most {SIM_MAX_CANDIDATES}')
+    if isinstance(refractory_us, bool) or not isinstance(refractory_us, (int, np.integer)) or not 0 <= refractory_us < SIM_T_LIMIT:
+        raise ValueError(f'refractory_us={refractory_us!r}: an integer in [0, 2^32) expected')
+    times = ints(times_us, 'times_us', None)
+    if times.ndim != 1:
+        raise ValueError(f'times_us: a list of integers expected, got shape {times.shape}')
+    if len(times):
+        if times.min() < 0 or times.max() >= SIM_T_LIMIT:
+            raise ValueError('times_us: times in [0, 2^32) expected (the .dat clock)')
+        if times[0] <= t_last:
+            raise ValueError(f'times_us: the first frame, at {int(times[0])}, is not later than the last frame of the state, at {int(t_last)}')
+        step = np.diff(times)
+        if len(step) and step.min() <= 0:
+            k = int(np.argmax(step <= 0))
+            raise ValueError(f'times_us: {int(times[k])} is followed by {int(times[k + 1])}; strictly increasing times expected')
+    return times, lut.astype(np.int32), th[0].astype(np.int32), th[1].astype(np.int32)
+
+
+def simulate_events(frames_u8, times_us, lut, theta_on, theta_off, refractory_us=0, state=None, ws_bytes=None):
+    """Luma frames on the device (uint8 [n, H, W]) with their times -> (records uint8 [m, 8], state) by the simulator's rule of DESIGN.md
+    section 1: per pixel a reference level m; between two frames the table value ``lut[v]`` moves linearly, and every multiple of the
+    pixel's threshold it passes on its way from m is an ON (rising) or OFF (falling) event at the integer time the line reaches it; an
+    event less than ``refractory_us`` behind the pixel's last kept one is dropped.  The records are .dat records ordered by time, then
+    pixel, then the event's number.  ``times_us``, ``lut``, ``theta_on``, ``theta_off`` are HOST data (lists / numpy / CPU tensors; a
+    threshold may be one integer): checked here by ``simulate_check`` (``ValueError``), then uploaded.
+    ``state`` (int64 on the device, layout in include/leod_hip.h: the counters, the time of the last frame, {m, t_keep} per pixel, the
+    last frame) carries a recording from call to call, with the same table and thresholds: None starts one, whose first frame emits
+    nothing; the given tensor is not modified, the returned one is new.  One launch counts, ONE read-back (the kept events per frame, with
+    the head of the state) sizes the output and the workspace exactly, then the emit launches.  ``ws_bytes`` (None: no bound) bounds the
+    workspace: a call that needs more takes the longest prefix of its frames that fits, then goes on with the rest, which changes nothing
+    but the launches; a single frame whose events do not fit raises ``LeodHipError`` naming the bytes it needs."""
+    _ck(frames_u8, torch.uint8, 'frames')
+    if frames_u8.dim() != 3:
+        raise LeodHipError(f'frames: uint8 [n, H, W] expected, got {tuple(frames_u8.shape)}')
+    n_frames, height, width = (int(v) for v in frames_u8.shape)
+    times, lut, th_on, th_off = simulate_check(height, width, times_us, lut, theta_on, theta_off, refractory_us)
+    if len(times) != n_frames:
+        raise ValueError(f'times_us: {len(times)} times for {n_frames} frames')
+    if n_frames > SIM_MAX_FRAMES:
+        raise ValueError(f'{n_frames} frames in one call; at most {SIM_MAX_FRAMES}')
+    dev = frames_u8.device
+    _, _, n_state, n_count, _ = simulate_query(0, height, width)
+    new = _filter_state(state, n_state, height, width)
+    if new is None:
+        new = torch.zeros((n_state,), dtype=torch.int64, device=dev)
+        new[5] = -1
+        new[SIM_STATE_HEAD + 1:SIM_STATE_HEAD + 2 * height * width:2] = -1
+    if n_frames == 0:
+        return torch.empty((0, 8), dtype=torch.uint8, device=dev), new
+    d_times, d_lut = torch.from_numpy(times).to(dev), torch.from_numpy(lut).to(dev)
+    d_on, d_off = torch.from_numpy(th_on).to(dev), torch.from_numpy(th_off).to(dev)
+    counts = torch.empty((n_count + n_frames,), dtype=torch.int64, device=dev)
+    refr = int(refractory_us)
+
+    def count(a, b):
+        check(_l().leod_simulate_count(_p(frames_u8[a:b]), b - a, height, width, _p(d_times[a:b]), _p(d_lut), _p(d_on), _p(d_off), refr,
+                                       _p(new), _p(counts), _stream()), 'simulate_events (count)')
+    count(0, n_frames)
+    host = torch.cat((new[:SIM_STATE_HEAD], counts[n_count:])).cpu().tolist()                    # the one read-back
+    seen, t_last, per = host[0], host[5], host[SIM_STATE_HEAD:]
+    if seen > 0 and int(times[0]) <= t_last:
+        raise ValueError(f'times_us: the first frame, at {int(times[0])}, is not later than the last frame of the state, at {t_last}')
+    limit = None if ws_bytes is None else int(ws_bytes)
+    need = lambda n: simulate_query(n, height, width)[4]                                         # noqa: E731
+    total = sum(per)
+    if total <= SIM_MAX_EVENTS and (limit is None or need(total) <= limit):
+        pieces = [(0, n_frames, total)]
+    else:
+        pieces, a, acc = [], 0, 0
+        for k, c in enumerate(per):
+            if c > SIM_MAX_EVENTS:
+                raise LeodHipError(f'simulate_events: frame {k} alone brings {c} events; at most {SIM_MAX_EVENTS} per interval')
+            if limit is not None and need(c) > limit:
+                raise LeodHipError(f'simulate_events: ws_bytes={limit}, and the {c} events of frame {k} alone need {need(c)} bytes')
+            if k > a and (acc + c > SIM_MAX_EVENTS or (limit is not None and need(acc + c) > limit)):
+                pieces.append((a, k, acc))
+                a, acc = k, 0
+            acc += c
+        pieces.append((a, n_frames, acc))
+    out = torch.empty((total, 8), dtype=torch.uint8, device=dev)
+    at = 0
+    for a, b, n in pieces:
+        if len(pieces) > 1:
+            count(a, b)                                          # the counts of the piece's own frames, from the state as it is now
+        t_base = int(times[a - 1]) if a > 0 else (t_last if seen > 0 else int(times[0]))
+        nbytes = need(n) if n else 0
+        ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev) if n else None
+        check(_l().leod_simulate_emit(_p(frames_u8[a:b]), b - a, height, width, _p(d_times[a:b]), _p(d_lut), _p(d_on), _p(d_off), refr,
+                                      _p(new), _p(counts), t_base, int(times[b - 1]), n, _p(ws), nbytes, _p(out[at:at + n]) if n else None,
+                                      n, _stream()), 'simulate_events (emit)')
+        at += n
+    return out, new
+
+
+def simulate_counters(state):
+    """The counters of a simulator state (one read-back): frames, kept, on, off, dropped, t_last."""
+    return _state_counters(state, _SIM_COUNTERS, SIM_STATE_HEAD, 'a simulator')
+
+
 # scratch of one piece of a chunk of ``survey_events``: the sort of csrc/pixel_sort.hpp, as for ``pixel_filter_events``
 SURVEY_WS_BYTES = PIXFILTER_WS_BYTES
 SURVEY_STATE_HEAD = 8
